@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: Mray/s (primary + shadow) on bunny.geom, 1920x1080, 256 spp.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 One step = one full frame of BASELINE config C3 (mesh-bunny layout: baked
@@ -20,8 +20,22 @@ its own bands, one RCCL gather + an on-GPU un-interleave assembles the frame
 on rank 0 (strong scaling; every gather inside the timed region, frame k's
 overlapping frame k+1's render from a second band buffer).
 
-Printed (rank 0, one JSON line): value = (primary + shadow rays of all ranks)
-x K / max-over-ranks wall time, plus
+A plain run does only what the headline needs: scene setup, one counting
+frame (the deterministic per-frame ray counts), W warmup steps, the K timed
+steps, and one JSON line (rank 0): value = (primary + shadow rays of all
+ranks) x K / max-over-ranks wall time, ms_per_step = that wall time / K.
+(With few steps the plain run starts its timed region on a GPU that has been
+busy for less time than under --full, whose extra launches precede it: C3 at
+--steps 20 --warmup 5 read 0.83 ms plain against 0.81 ms with --full on one
+MI355X, and 0.81 ms plain from --steps 100 on.)
+--dump-outputs DIR writes the frame the last timed step left in the frame
+buffer (what a caller of the timed call receives) as DIR/frame.npy, float32
+(H, W, 3); a frame over 60 MB is cut to a fixed seeded sample of whole rows,
+their indices beside it in DIR/frame_rows.npy. Scene, camera and samples are
+deterministic, so two runs with the same arguments render the same inputs.
+
+--full adds, in passes of their own around the same timed region, the first
+frame's and a camera change's cost, the multi-GPU frame check, and
   roofline     — the render kernels of the call (C3-C5: the merged kernel
                  k_render_mix1), timed with HIP events inside the library
                  (RT_FLAG_TIMING, the call's stream) in a pass after the
@@ -34,7 +48,9 @@ x K / max-over-ranks wall time, plus
                  cycles; HBM bytes per call from the same summary beside it;
   cpu_baseline — the fp64 oracle (the reference algorithm: linear objects,
                  brute-force mesh, scanline thread pool) on this host, 1 spp on
-                 a bounded row subsample of the same frame (rank 0, N = 1 only).
+                 a bounded row subsample of the same frame (rank 0, N = 1 only),
+  fp64_parity / bvh_path — the same frame in the float64 parity mode and on
+                 the BVH-only path (C2 / C3, N = 1).
 """
 import argparse
 import json
@@ -81,22 +97,30 @@ def parse():
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame to DIR/frame.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: roofline passes, first-frame / camera-change cost, "
+                         "fp64_parity / bvh_path, the CPU baselines, the multi-GPU frame check")
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS),
                     help="BASELINE.json config (C3 = the headline metric)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--grid", type=int, default=None, help="akGrid m (spp = m*m)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the fp64_parity / bvh_path sub-measurements after the timed region")
+                    help="with --full: skip the fp64_parity / bvh_path sub-measurements after the timed region")
     ap.add_argument("--bvh", default="sah", choices=["sah", "ploc"],
                     help="mesh BVH builder: host binned SAH (default) or device PLOC")
     ap.add_argument("--flags", type=int, default=0, help="rt_options.flags (1 = any-hit shadows)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp64"],
                     help="fp32 = the performance kernels (the headline); fp64 = the parity mode the Nim "
                          "binding defaults to (bit-exact against the oracle): the cost of exactness")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(scene, width, height, target_s, bvh=False):
@@ -286,6 +310,25 @@ def load_pmc(workload_key):
     return e
 
 
+DUMP_BYTES = 60_000_000  # per-run cap of what --dump-outputs writes
+
+
+def dump_outputs(path, fb, width, height):
+    """DIR/frame.npy: the device frame buffer `fb` as float32 (rows, width, 3).
+    A frame over DUMP_BYTES keeps a fixed seeded sample of whole rows (the
+    same rows for the same frame size), listed in DIR/frame_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frame = fb.view(height, width, 3)
+    keep = DUMP_BYTES // (width * 3 * 4)
+    if keep < height:
+        import torch
+        rows = np.sort(np.random.default_rng(0).choice(height, size=keep, replace=False))
+        frame = frame[torch.from_numpy(rows).to(frame.device)]
+        np.save(os.path.join(path, "frame_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "frame.npy"), frame.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     args = parse()
     import torch
@@ -330,8 +373,10 @@ def main():
     stream = torch.cuda.current_stream()
     # the first frame of this scene and image size also allocates the
     # per-call buffers and reads the camera-ray list size once (every frame
-    # builds the lists themselves): timed on its own, beside the steps
-    if not distributed:
+    # builds the lists themselves): --full times it on its own, beside the
+    # steps (a plain run's counting frame below is its first frame)
+    full = args.full
+    if not distributed and full:
         fb0 = torch.zeros(H * W * 3, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -390,10 +435,12 @@ def main():
     # node visits / triangle tests of one instrumented launch of the BVH path
     # (k_render_fast<true>, RT_FLAG_COUNT_TRAVERSAL | RT_FLAG_NO_BINNING) —
     # a model of what a per-ray BVH tracer would read, not the timed kernels
-    copts = dataclasses.replace(opts, flags=opts.flags | RT_FLAG_COUNT_TRAVERSAL | RT_FLAG_NO_BINNING,
-                                precision=Precision.fp32)
-    ds.render_bands_device(copts, local_buf, BAND_H, rank, world, stream=stream, stats=True)
-    counters = ds.last_counters()
+    counters = None
+    if full:
+        copts = dataclasses.replace(opts, flags=opts.flags | RT_FLAG_COUNT_TRAVERSAL | RT_FLAG_NO_BINNING,
+                                    precision=Precision.fp32)
+        ds.render_bands_device(copts, local_buf, BAND_H, rank, world, stream=stream, stats=True)
+        counters = ds.last_counters()
     for _ in range(max(0, args.warmup)):
         step()
     finish_frame()
@@ -426,6 +473,54 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     call_ms = ev0.elapsed_time(ev1) / max(1, args.steps)
+    # the last timed step's frame, before any later pass writes the buffer
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fb, W, H)
+
+    value = rays_frame * args.steps / elapsed / 1e6
+    head = {
+        "metric": ("Mray/s (primary+shadow) on bunny.geom 1080p/256spp; 1/2/4/8-GPU scaling"
+                   if args.config == "C3" else f"Mray/s (primary+shadow) on {args.config}"),
+        "value": round(value, 2),
+        "unit": "Mray/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64" if fp64 else "f32",
+        "data": {"bunny": "synthetic rays over the reference's bunny.geom fixture (69,451 triangles)",
+                 "boxes2": "synthetic rays over the reference's boxes2.nim scene",
+                 "torus": "synthetic rays over a deterministic procedural 1M-triangle torus",
+                 "mix": "synthetic rays over a test scene of this build (mesh-mix)"}[scene_name],
+    }
+    config = {
+        "workload": (f"{desc}, {W}x{H}, akGrid {m}x{m} = {m * m} spp, "
+                     + ("fp64 parity mode (k_render_px64: the reference's arithmetic, bit-exact "
+                        "against the oracle), " if fp64 else "fp32, ")
+                     + (f"{BAND_H}-row bands round-robin over {world} ranks (one GPU each) + RCCL gather "
+                        "to rank 0" if distributed else "one whole-frame call per step on one GPU")
+                     + "; every step builds its camera-dependent data on the device"),
+        "width": W, "height": H, "spp": m * m, "triangles": info["num_triangles"],
+        "bvh_nodes": info["num_bvh_nodes"], "primary_rays_per_frame": prim_frame,
+        "shadow_rays_per_frame": shadow_frame, "parallelism": f"bands{world}",
+        "scene_setup_s": round(setup_s, 3), "scene_setup_ms_lib": round(info["build_ms"], 1),
+        "bvh_builder": {"sah": "host binned SAH", "ploc": "device PLOC"}[args.bvh],
+    }
+    # build provenance: the library's embedded source hash against this tree's
+    build = {"library_sources": library_source_hash(), "tree_sources": kernel_source_hash(),
+             "match": library_source_hash() == kernel_source_hash()}
+    if not full:
+        if rank == 0:
+            print(json.dumps({**head, "config": config, "call_ms": round(call_ms, 4), "build": build}),
+                  file=json_out, flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     lean_groups, general_groups = ds.last_split()
     kinds = ds.last_lean_kernel()
     lean_k = {0: None, 1: "k_render_lean", 2: "k_render_lean1q (one-plane lean pixels)", 3: None}[kinds & 3]
@@ -498,7 +593,6 @@ def main():
                                        "through the BVH (wave-coherent traversal, fp32), no per-pixel or light-cell "
                                        "lists — the path of scenes outside the one-mesh / one-plane envelope")
 
-    value = rays_frame * args.steps / elapsed / 1e6
     # SURVEY 8(d)'s per-ray BVH byte model over this launch's rays (what a
     # per-ray BVH tracer would read; these kernels skip most of it)
     bvh_model_bytes = (counters["lane_node_visits"] * 2 * SURVEY_BOX_BYTES
@@ -544,46 +638,13 @@ def main():
     })
 
     if rank == 0:
-        out = {
-            "metric": ("Mray/s (primary+shadow) on bunny.geom 1080p/256spp; 1/2/4/8-GPU scaling"
-                       if args.config == "C3" else f"Mray/s (primary+shadow) on {args.config}"),
-            "value": round(value, 2),
-            "unit": "Mray/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64" if fp64 else "f32",
-            "data": {"bunny": "synthetic rays over the reference's bunny.geom fixture (69,451 triangles)",
-                     "boxes2": "synthetic rays over the reference's boxes2.nim scene",
-                     "torus": "synthetic rays over a deterministic procedural 1M-triangle torus",
-                     "mix": "synthetic rays over a test scene of this build (mesh-mix)"}[scene_name],
-            "config": {
-                "workload": (f"{desc}, {W}x{H}, akGrid {m}x{m} = {m * m} spp, "
-                             + ("fp64 parity mode (k_render_px64: the reference's arithmetic, bit-exact "
-                                "against the oracle), " if fp64 else "fp32, ")
-                             + (f"{BAND_H}-row bands round-robin over {world} ranks (one GPU each) + RCCL gather "
-                                "to rank 0" if distributed else "one whole-frame call per step on one GPU")
-                             + "; every step builds its camera-dependent data on the device"),
-                "width": W, "height": H, "spp": m * m, "triangles": info["num_triangles"],
-                "bvh_nodes": info["num_bvh_nodes"], "primary_rays_per_frame": prim_frame,
-                "shadow_rays_per_frame": shadow_frame, "parallelism": f"bands{world}",
-                "scene_setup_s": round(setup_s, 3), "scene_setup_ms_lib": round(info["build_ms"], 1),
-                "first_frame_ms": None if first_frame_ms is None else round(first_frame_ms, 3),
-                "camera_change_frame_ms": None if camera_change_ms is None else round(camera_change_ms, 3),
-                "lean_pixel_groups": lean_groups, "general_pixel_groups": general_groups,
-                "batched_general_groups": batched_groups, "batch_fallback_groups": batch_fallback,
-                "bvh_builder": {"sah": "host binned SAH", "ploc": "device PLOC"}[args.bvh],
-            },
-            "roofline": roof,
-            "cpu_baseline": None,
-            # build provenance: the library's embedded source hash against this tree's
-            "build": {"library_sources": library_source_hash(), "tree_sources": kernel_source_hash(),
-                      "match": library_source_hash() == kernel_source_hash()},
-        }
+        config.update({
+            "first_frame_ms": None if first_frame_ms is None else round(first_frame_ms, 3),
+            "camera_change_frame_ms": None if camera_change_ms is None else round(camera_change_ms, 3),
+            "lean_pixel_groups": lean_groups, "general_pixel_groups": general_groups,
+            "batched_general_groups": batched_groups, "batch_fallback_groups": batch_fallback,
+        })
+        out = {**head, "config": config, "roofline": roof, "cpu_baseline": None, "build": build}
         if frame_check is not None:
             out["frame_check"] = frame_check
         out.update(extra)

@@ -84,7 +84,33 @@ def objconv(obj_path, geom_path, slash_indices=False):
                               f.ctypes.data_as(C.POINTER(C.c_int32)), f.shape[0]))
 
 
+_geom_tmp = None
+
+
+def _remove_quietly(path):
+    try:
+        os.remove(path)
+    except OSError:
+        pass
+
+
 def default_geom_path():
-    """The committed copy of the reference's test/bunny.geom fixture."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    return os.path.normpath(os.path.join(here, "..", "..", "tests", "golden", "bunny.geom"))
+    """The committed copy of the reference's test/bunny.geom fixture. It is
+    stored xz-compressed (tests/golden/bunny.geom.xz, the same bytes) and
+    unpacked once per process into a temporary file of its own, removed at
+    exit: the native reader (rt_load_geom) takes a path."""
+    global _geom_tmp
+    if _geom_tmp is None or not os.path.exists(_geom_tmp):
+        import atexit
+        import lzma
+        import tempfile
+        here = os.path.dirname(os.path.abspath(__file__))
+        src = os.path.normpath(os.path.join(here, "..", "..", "tests", "golden", "bunny.geom.xz"))
+        with lzma.open(src, "rb") as fin:
+            data = fin.read()
+        fd, tmp = tempfile.mkstemp(prefix="rtmi_bunny_", suffix=".geom")
+        with os.fdopen(fd, "wb") as fout:
+            fout.write(data)
+        atexit.register(_remove_quietly, tmp)
+        _geom_tmp = tmp
+    return _geom_tmp

@@ -24,6 +24,9 @@ def header_functions():
 def test_header_symbols_exported():
     names = header_functions()
     assert len(names) >= 15
+    # through the loader first: it brings in PyTorch's HIP runtime before the
+    # library, so GPU tests later in the same process share one runtime with it
+    lib()
     raw = C.CDLL(LIB_PATH)
     missing = [n for n in names if not hasattr(raw, n)]
     assert not missing, missing

@@ -127,7 +127,10 @@ def test_ppm_writer(tmp_path, oracle_mod):
 
 def test_bunny_fixture():
     # test/bunny.geom == src/loaders/bunny.geom
-    p = os.path.join(GOLDEN, "bunny.geom")
+    # (committed xz-compressed; default_geom_path() unpacks the same bytes)
+    from rtmi.loaders import default_geom_path
+    assert os.path.exists(os.path.join(GOLDEN, "bunny.geom.xz"))
+    p = default_geom_path()
     assert hashlib.sha256(open(p, "rb").read()).hexdigest() == \
         "203ed181847583e4b22b41d55c446142a8456bb08d9ce275d11bcc19759bdbe9"
     from rtmi.loaders import readGeom

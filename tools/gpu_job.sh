@@ -6,7 +6,7 @@
 # Stages, run in order, each GPU step under its own time limit, chained so
 # nothing runs after a failure (outputs under gpurun_out/$OUT):
 #   tests            pytest -m gpu over $TESTS (default: tests)
-#   bench:CFG[:fp64] one bench.py line (--config CFG, $BENCH_ARGS) -> bench_<cfg>[_fp64].json
+#   bench:CFG[:fp64] one bench.py --full line (--config CFG, $BENCH_ARGS) -> bench_<cfg>[_fp64].json
 #   prof:CFG[:fp64]  rocprofv3 --kernel-trace --stats of that bench command ($PROF_ARGS) -> prof_<cfg>/
 #   pmc:CFG[:fp64|:bvh] three PMC passes (FETCH_SIZE / WRITE_SIZE / SQ issue counters;
 #                    fp64 adds a fourth: the F64 op counts; bvh = --flags 8, RT_FLAG_NO_BINNING),
@@ -38,26 +38,26 @@ for st in ${STAGES:-tests}; do
         || { tail -40 $O/tests.log; exit 1; }
       tail -2 $O/tests.log ;;
     bench)
-      timeout -k 10 $T python bench.py --config ${cfg:-C3} $pa ${BENCH_ARGS:-} > $O/bench_$c$sfx.json 2> $O/bench_$c$sfx.err \
+      timeout -k 10 $T python bench.py --full --config ${cfg:-C3} $pa ${BENCH_ARGS:-} > $O/bench_$c$sfx.json 2> $O/bench_$c$sfx.err \
         || { tail -20 $O/bench_$c$sfx.err; exit 1; }
       cat $O/bench_$c$sfx.json ;;
     prof)
-      timeout -k 10 $T rocprofv3 --kernel-trace --stats -d $O/prof_$c$sfx -o p -f csv -- python3 bench.py --config ${cfg:-C3} $pa \
+      timeout -k 10 $T rocprofv3 --kernel-trace --stats -d $O/prof_$c$sfx -o p -f csv -- python3 bench.py --full --config ${cfg:-C3} $pa \
         --steps ${PROF_STEPS:-5} --warmup 1 --no-cpu ${PROF_ARGS:-} > $O/prof_$c$sfx.json 2> $O/prof_$c$sfx.err || { tail -20 $O/prof_$c$sfx.err; exit 1; }
       cat $O/prof_$c$sfx.json ;;
     pmc)
       P=$O/pmc_$c$sfx
       mkdir -p $P
       S="--config ${cfg:-C3} $pa --steps 2 --warmup 0 --no-cpu --no-extra"
-      timeout -s KILL $T rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$K" -d $P/fetch -o p -f csv -- python3 bench.py $S > /dev/null 2> $P/fetch.err \
-        && timeout -s KILL $T rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$K" -d $P/write -o p -f csv -- python3 bench.py $S > /dev/null 2> $P/write.err \
+      timeout -s KILL $T rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$K" -d $P/fetch -o p -f csv -- python3 bench.py --full $S > /dev/null 2> $P/fetch.err \
+        && timeout -s KILL $T rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$K" -d $P/write -o p -f csv -- python3 bench.py --full $S > /dev/null 2> $P/write.err \
         && timeout -s KILL $T rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-             --kernel-include-regex "$K" -d $P/sq -o p -f csv -- python3 bench.py $S > /dev/null 2> $P/sq.err \
+             --kernel-include-regex "$K" -d $P/sq -o p -f csv -- python3 bench.py --full $S > /dev/null 2> $P/sq.err \
         || { echo "pmc $c$sfx failed"; tail -5 $P/*.err; exit 1; }
       # float64: the F64 op mix (an F64 VALU instruction issues over 4 cycles, not 2)
       if [ "$prec" = fp64 ]; then
         timeout -s KILL $T rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT64 \
-             --kernel-include-regex "$K" -d $P/f64 -o p -f csv -- python3 bench.py $S > /dev/null 2> $P/f64.err \
+             --kernel-include-regex "$K" -d $P/f64 -o p -f csv -- python3 bench.py --full $S > /dev/null 2> $P/f64.err \
           || { echo "pmc $c$sfx f64 failed"; tail -5 $P/f64.err; exit 1; }
       fi
       echo "pmc $c$sfx done" ;;
@@ -67,7 +67,7 @@ for st in ${STAGES:-tests}; do
           v=${spec%%@*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*@}
           tag=$(echo "$spec" | tr '@=,' '___')
           L=""; [ $v != base ] && L=tools/ab/$v.so
-          env RTMI_LIB=$L ${envs//,/ } timeout -k 10 $T python bench.py --config ${AB_CONFIG:-C3} --no-cpu \
+          env RTMI_LIB=$L ${envs//,/ } timeout -k 10 $T python bench.py --full --config ${AB_CONFIG:-C3} --no-cpu \
             ${AB_ARGS:---steps 20 --warmup 3} > $O/ab_${tag}_$i.json 2> $O/ab_${tag}_$i.err || { tail -20 $O/ab_${tag}_$i.err; exit 1; }
           echo "$spec $i $(grep -o '"ms_per_step": [0-9.]*' $O/ab_${tag}_$i.json) $(grep -o '"kernel_ms": [0-9.]*' $O/ab_${tag}_$i.json)"
         done
