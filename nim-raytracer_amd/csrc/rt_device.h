@@ -1098,6 +1098,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEVELS > 1 
   using R = double;
   (void)params_by_value;  // read through rparams()
   const RT_CONST RenderParams<R>& p = rparams<R>();
+  static_assert(3 * P <= 64, "one summing lane per pixel and colour channel: 3 P lanes of the wave");
   constexpr int kRow = 66;  // 16-B aligned rows; row stride 4 banks apart: the 3P summing lanes' reads never conflict
   __shared__ __attribute__((aligned(16))) double sbuf[4][P * 3 * kRow];
   const int lane = (int)__lane_id();

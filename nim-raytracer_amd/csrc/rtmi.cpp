@@ -350,6 +350,8 @@ struct rt_scene {
     grids.release();
     lrec.release();
     grec.release();
+    sh64.release();
+    sh64_ready = false;
     grid_off.release();
     grid_ent.release();
     obj_grids.release();

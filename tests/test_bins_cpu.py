@@ -12,6 +12,7 @@ import math
 import numpy as np
 import pytest
 
+import cameras
 from rtmi import scenes
 from rtmi._lib import lib
 from rtmi.glm import X_AXIS, Y_AXIS, degToRad, inverse, mat4, rotate, scale, translate, vec3
@@ -69,9 +70,118 @@ def _bunny():
 
 MESHES = {"bunny": _bunny, "rotated_torus": _rotated_torus}
 
+# Per camera (tests/cameras.py, on the rotated torus; "std": the scenes' own
+# camera, both meshes) the least population each completeness test must find:
+# without it a test could pass on rays that meet nothing. "std" keeps the
+# values the tests always had; the others are about half of what the float64
+# brute-force side of the test found for that camera (the figures in the
+# comments, profiles/cameras/bins_cpu_population.jsonl;
+# RTMI_POPULATION_LOG=<file> appends them). The host builders
+# decline `straddle` and `behind` (a vertex at or behind the camera plane),
+# so they are in no list; a camera that yields nothing for a family is left
+# out of that family by name.
+PIXEL_LIST_HITS = {  # faces hit by the 800 rays
+    "std": 200,
+    "closeup": 350,       # 708
+    "closeup_roll": 340,  # 696
+    "topdown": 330,       # 669
+    "grazing": 380,       # 771
+    "below": 350,         # 716
+    "far_side": 200,      # 417
+    "fov_wide": 230,      # 463
+    "fov_narrow": 310,    # 637
+    "fov_narrow_aimed": 400,  # 800: every ray meets the mesh
+    "beside": 350,        # 707
+    "on_plane": 340,      # 698
+}
+# (fov_narrow_aimed sees the mesh only, no plane: in neither shadow family)
+SHADOW_SKIPS = {  # (share of the 480 x 270 pixels with a skip bit, checked shadow-border pixels)
+    "std": (0.3, 100),
+    "closeup": (0.19, 190),       # 0.391, 394
+    "closeup_roll": (0.23, 320),  # 0.462, 649
+    "topdown": (0.27, 410),       # 0.548, 826
+    "grazing": (0.44, 9),         # 0.881, 19 (the shadow is a sliver along the horizon)
+    "below": (0.42, 210),         # 0.856, 434
+    "far_side": (0.49, 44),       # 0.989, 88
+    "fov_wide": (0.49, 60),       # 0.984, 124
+    "fov_narrow": (0.40, 80),     # 0.803, 160
+    "beside": (0.21, 260),        # 0.427, 530
+    "on_plane": (0.43, 11),       # 0.869, 23
+}
+# closeup, closeup_roll, fov_narrow and beside see no pixel with a shadow
+# list for one of the two lights (the test wants some for each): left out
+SHADOW_LISTS = {  # (pixels with a list, faces hit by the checked shadow rays)
+    "std": (100, 50),
+    "topdown": (13500, 1400),  # 27115, 2891
+    "grazing": (730, 730),     # 1477, 1472
+    "below": (12000, 1300),    # 24368, 2756
+    "far_side": (400, 770),    # 800, 1548
+    "fov_wide": (1000, 1200),  # 2067, 2402
+    "on_plane": (630, 730),    # 1271, 1461
+}
 
-@pytest.mark.parametrize("name", list(MESHES))
-def test_pixel_lists_hold_every_hit_face(name):
+
+def _cases(table, tilted=False):
+    """The standard camera on both meshes (ids as before the camera table),
+    then the table's other cameras on the rotated torus."""
+    if tilted:
+        std = [pytest.param("bunny", False, "std", id="bunny-False"),
+               pytest.param("rotated_torus", True, "std", id="rotated_torus-True")]
+        return std + [pytest.param("rotated_torus", True, c, id=f"rotated_torus-True-{c}") for c in table if c != "std"]
+    std = [pytest.param(n, "std", id=n) for n in MESHES]
+    return std + [pytest.param("rotated_torus", c, id=f"rotated_torus-{c}") for c in table if c != "std"]
+
+
+def _camera(mesh, cam):
+    """(flat column-major cameraToWorld, fov) of camera `cam` for `mesh`."""
+    std = scenes.mesh_bunny().cameraToWorld
+    if cam == "std":
+        return _m(std), 50.0
+    c2w, fov = cameras.camera_table(mesh, std)[cam]
+    return _m(c2w), fov
+
+
+@pytest.mark.parametrize("name", ["scene_torus", "rotated_torus"])
+def test_camera_table_preconditions(name):
+    """The table's cameras are what their names say, for the torus of
+    test_gpu_cameras.py's scene and for the rotated torus used here: checked
+    from the world box and the vertices in numpy."""
+    mesh = (scenes._mesh_scene(scenes.torus_mesh(24, 12), "torus", (0.9, 0.5, 0.2)).objects[0].geometry
+            if name == "scene_torus" else _rotated_torus())
+    table = cameras.camera_table(mesh, scenes.mesh_bunny().cameraToWorld)
+    lo, hi = cameras.world_box(mesh)
+    corners, verts = cameras.box_corners(lo, hi), cameras.world_vertices(mesh)
+    d = {cam: (cameras.depths(c2w, corners), cameras.depths(c2w, verts)) for cam, (c2w, _) in table.items()}
+    assert abs(d["closeup"][0].min() - 0.05) < 1e-9 and abs(d["closeup_roll"][0].min() - 0.3) < 1e-9
+    assert d["straddle"][1].min() < -0.5 and d["straddle"][1].max() > 0.5
+    assert d["beside"][0].min() < -0.05 and d["beside"][1].min() > 0.05  # the box is cut, every vertex in front
+    assert d["behind"][0].max() < -1.0
+    assert table["on_plane"][0][3, 1] == 0.0 and 0.0 < table["grazing"][0][3, 1] <= 0.05
+    assert table["below"][0][3, 1] < 0.0
+    assert np.allclose(-table["topdown"][0][2, :3], [0.0, -1.0, 0.0])
+    assert table["fov_wide"][1] == 120.0 and table["fov_narrow"][1] == table["fov_narrow_aimed"][1] == 3.0
+    for cam, (c2w, _) in table.items():  # orthonormal, right-handed
+        r = c2w[:3, :3]
+        assert np.allclose(r @ r.T, np.eye(3), atol=1e-12) and np.linalg.det(r) > 0.0, cam
+    for cam in set(table) - set(cameras.DECLINED_ON_DEVICE):
+        assert d[cam][0].min() > 0.0, cam
+    for cam in set(table) - set(cameras.DECLINED_ON_HOST):
+        assert d[cam][1].min() > 0.0, cam
+    # the cameras of this file's tables exist
+    assert set(PIXEL_LIST_HITS) | set(SHADOW_SKIPS) | set(SHADOW_LISTS) <= set(table) | {"std"}
+
+
+def _log_population(what, name, cam, value):
+    import json
+    import os
+    path = os.environ.get("RTMI_POPULATION_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"what": what, "mesh": name, "camera": cam, "value": float(value)}) + "\n")
+
+
+@pytest.mark.parametrize("name,cam", _cases(PIXEL_LIST_HITS))
+def test_pixel_lists_hold_every_hit_face(name, cam):
     L = lib()
     f = L.rtmi_test_pixel_bins
     f.restype = C.c_int64
@@ -79,9 +189,8 @@ def test_pixel_lists_hold_every_hit_face(name):
     v9 = _faces(mesh)
     nf = len(v9)
     o2w, w2o = _m(mesh.objectToWorld), _m(mesh.worldToObject)
-    cam = scenes.mesh_bunny().cameraToWorld
-    c2w = _m(cam)
-    W, H, fov = 160, 90, 50.0
+    c2w, fov = _camera(mesh, cam)
+    W, H = 160, 90
     off = np.zeros(W * H + 1, np.int32)
     cap = 4 * nf * 64 + 64
     ent = np.zeros(cap, np.int32)
@@ -117,7 +226,8 @@ def test_pixel_lists_hold_every_hit_face(name):
         assert not missing, (name, x, y, sorted(missing)[:5])
         checked += 1
         hits_total += len(hit)
-    assert hits_total > 200  # the rays really meet the mesh
+    _log_population("pixel_lists", name, cam, hits_total)
+    assert hits_total > PIXEL_LIST_HITS[cam]  # the rays really meet the mesh
 
 
 @pytest.mark.parametrize("name", list(MESHES))
@@ -184,8 +294,8 @@ def _tilted_plane():
     return m, inverse(m)
 
 
-@pytest.mark.parametrize("name,tilted", [("bunny", False), ("rotated_torus", True)])
-def test_shadow_skips_are_conservative(name, tilted):
+@pytest.mark.parametrize("name,tilted,cam", _cases(SHADOW_SKIPS, tilted=True))
+def test_shadow_skips_are_conservative(name, tilted, cam):
     """A pixel's skip bit for a light (rt_bins.h build_shadow_skips) promises
     that no shadow ray to that light from a camera hit in the pixel meets a
     face: checked for random samples (and the pixel corners) of skipped
@@ -198,17 +308,18 @@ def test_shadow_skips_are_conservative(name, tilted):
     nf = len(v9)
     o2w, w2o = _m(mesh.objectToWorld), _m(mesh.worldToObject)
     sc = scenes.mesh_bunny()
-    c2w = _m(sc.cameraToWorld)
+    c2w, fov = _camera(mesh, cam)
     po2w, pw2o = _tilted_plane() if tilted else (mat4(1.0), mat4(1.0))
     planes = np.concatenate([_m(po2w), _m(pw2o)])
     dirs = np.ascontiguousarray(np.concatenate([np.asarray(l.dir[:3], np.float64) for l in sc.lights]))
-    W, H, fov, bias = 480, 270, 50.0, 1e-4
+    W, H, bias = 480, 270, 1e-4
     out = np.zeros((W * H + 3) // 4, np.uint32)
     n = f(v9.ctypes.data_as(C.c_void_p), C.c_int64(nf), o2w.ctypes.data_as(C.c_void_p),
           w2o.ctypes.data_as(C.c_void_p), c2w.ctypes.data_as(C.c_void_p), C.c_double(fov), W, H,
           planes.ctypes.data_as(C.c_void_p), 1, dirs.ctypes.data_as(C.c_void_p), len(sc.lights), C.c_double(bias),
           out.ctypes.data_as(C.c_void_p))
-    assert n > 0.3 * W * H  # most ground pixels skip at least one light
+    _log_population("shadow_skips.n", name, cam, n)
+    assert n > SHADOW_SKIPS[cam][0] * W * H  # (standard camera: most ground pixels skip at least one light)
     bits = (out.view(np.uint8)[:W * H]).astype(np.int64)
     C2W, W2O, P2W, W2P = _cols(c2w), _cols(w2o), _cols(_m(po2w)), _cols(_m(pw2o))
     N = P2W[:3, 1]
@@ -239,11 +350,12 @@ def test_shadow_skips_are_conservative(name, tilted):
             hit = _hits(v9, ro, rd)
             assert len(hit) == 0, (name, li, x, y, hit[:5])
             near += k < len(edge)
-    assert near > 100
+    _log_population("shadow_skips.near", name, cam, near)
+    assert near > SHADOW_SKIPS[cam][1]
 
 
-@pytest.mark.parametrize("name,tilted", [("bunny", False), ("rotated_torus", True)])
-def test_shadow_lists_hold_every_hit_face(name, tilted):
+@pytest.mark.parametrize("name,tilted,cam", _cases(SHADOW_LISTS, tilted=True))
+def test_shadow_lists_hold_every_hit_face(name, tilted, cam):
     """A pixel's shadow list for a light (rt_bins.h build_shadow_skips, sl)
     promises every face a shadow ray to that light from a camera hit in the
     pixel can meet: checked for random samples (and the pixel corners) of
@@ -256,12 +368,12 @@ def test_shadow_lists_hold_every_hit_face(name, tilted):
     nf = len(v9)
     o2w, w2o = _m(mesh.objectToWorld), _m(mesh.worldToObject)
     sc = scenes.mesh_bunny()
-    c2w = _m(sc.cameraToWorld)
+    c2w, fov = _camera(mesh, cam)
     po2w, pw2o = _tilted_plane() if tilted else (mat4(1.0), mat4(1.0))
     planes = np.concatenate([_m(po2w), _m(pw2o)])
     dirs = np.ascontiguousarray(np.concatenate([np.asarray(l.dir[:3], np.float64) for l in sc.lights]))
     nl = len(sc.lights)
-    W, H, fov, bias = 480, 270, 50.0, 1e-4
+    W, H, bias = 480, 270, 1e-4
     sl = np.zeros(W * H * nl * 2, np.int32)
     cap = 1 << 22
     ent = np.zeros(cap, np.int32)
@@ -269,7 +381,8 @@ def test_shadow_lists_hold_every_hit_face(name, tilted):
           w2o.ctypes.data_as(C.c_void_p), c2w.ctypes.data_as(C.c_void_p), C.c_double(fov), W, H,
           planes.ctypes.data_as(C.c_void_p), 1, dirs.ctypes.data_as(C.c_void_p), nl, C.c_double(bias),
           sl.ctypes.data_as(C.c_void_p), ent.ctypes.data_as(C.c_void_p), C.c_int64(cap))
-    assert n > 100, n
+    _log_population("shadow_lists.n", name, cam, n)
+    assert n > SHADOW_LISTS[cam][0], n
     sl = sl.reshape(W * H, nl, 2)
     C2W, W2O, P2W, W2P = _cols(c2w), _cols(w2o), _cols(_m(po2w)), _cols(_m(pw2o))
     N = P2W[:3, 1]
@@ -301,4 +414,5 @@ def test_shadow_lists_hold_every_hit_face(name, tilted):
                 hits_seen += len(hit)
                 missing = set(hit.tolist()) - lst
                 assert not missing, (name, li, x, y, sorted(missing)[:5])
-    assert hits_seen > 50, hits_seen
+    _log_population("shadow_lists.hits", name, cam, hits_seen)
+    assert hits_seen > SHADOW_LISTS[cam][1], hits_seen
