@@ -227,6 +227,13 @@ typedef struct rt_options {
  * lights their light-grid cells), each pixel's samples still summed in sample
  * order. The image and Stats are the same, bit for bit. */
 #define RT_FLAG_F64_PER_LANE 0x4000u
+/* One-plane two-class launches: do not classify the lean pixels. By default
+ * the per-call build proves, in the float32 arithmetic of the lean kernel,
+ * which lean pixels have samples that all hit the plane unshadowed or all
+ * miss it; the kernel writes such a pixel's fixed sum of one constant without
+ * running its sample loop. The image and Stats are the same, bit for bit
+ * (tests/test_gpu_uniform.py). */
+#define RT_FLAG_NO_UNIFORM 0x8000u
 
 /* Stats (src/renderer/stats.nim:4-13) plus ray counts for Mray/s. */
 typedef struct rt_stats {
@@ -497,6 +504,12 @@ int rt_scene_last_batch(rt_scene *scene, int64_t *batched_groups, int64_t *fallb
  * 0 otherwise) — mask with 0x1f to compare the kernel kinds. Host-side
  * bookkeeping, no wait. */
 int rt_scene_last_lean_kernel(rt_scene *scene, int32_t *kind);
+/* Of the last render call's lean pixel groups (rt_scene_last_split counts
+ * them all): how many the per-call build proved uniform-lit and uniform-sky,
+ * so that the lean kernel skipped their sample loops. Both 0 when the call
+ * classified nothing (RT_FLAG_NO_UNIFORM, not a one-plane two-class launch).
+ * Waits for the call. */
+int rt_scene_last_uniform(rt_scene *scene, int32_t *lit, int32_t *sky);
 
 /* ---- helpers ----------------------------------------------------------- */
 

@@ -7,6 +7,8 @@
 
 #include <math.h>
 
+#include "rt_common.h"
+
 namespace rtmi {
 namespace bg {
 
@@ -225,6 +227,100 @@ __host__ __device__ inline unsigned rect_skip_bits(const SkipCam& c, const SkipP
 __host__ __device__ inline unsigned pixel_skip_bits(const SkipCam& c, const SkipPlaneC* planes, int nplanes,
                                                     const SkipGrid* grids, int nl, unsigned have, int x, int y) {
   return rect_skip_bits(c, planes, nplanes, grids, nl, have, x, y, x, y);
+}
+
+// ---- uniform lean pixels of the one-plane kernel (rt_fast.h lean1q_loop) --
+//
+// A lean pixel of a one-plane launch whose m x m samples provably all take
+// the same branch of lean1q_loop is a fixed sum of one constant: every camera
+// ray hits the plane and no shadow ray is occluded by it (uniform-lit, the
+// constant is albedo x irradiance), or every camera ray misses (uniform-sky,
+// the background). This is a proof about the kernel's FLOAT32 arithmetic, so
+// it evaluates the kernel's own expressions from the kernel's own parameter
+// values (FastParams), with fmaf exactly where the kernel has one.
+//
+// The kernel, per sample of column index i and row index j (0 .. m - 1):
+//   px = x + fma(i, st, of)      cx = (px - cam_b) * cam_a
+//   py = y + fma(j, st, of)      cy = (cam_d - py) * cam_c
+//   N  = fma(cy, c7, fma(cx, c4, -c10))
+//   rl = rsq(fma(cy, cy, fma(cx, cx, 1)))      dy = N * rl
+//   t  = nroy * rcp(dy)
+//   hit = |dy| > 1e-6 and t in [-0, +inf)      (class test: -0, +0, +denormal, +normal)
+// Every step from i to N is a monotone function followed by a monotone
+// rounding, and so is every step from j to N, and the direction does not
+// depend on the other index (it is the sign of st cam_a c4, resp. of
+// -st cam_c c7). So N over the pixel's samples lies between its values at the
+// four corner samples (indices 0 and m - 1), which are evaluated here; cx^2
+// and cy^2 are largest at an end of their ranges.
+//
+// Both rules need N finite and of one strict sign at the four corners, with
+// |N| <= 1e10, and 1e-20 <= |nroy| <= 1e20. As rl <= 1 (its argument is >= 1;
+// v_rsq is within 1 ulp), |dy| <= 1.0000003e10, so |t| >= 0.99e-30: t is a
+// normal number, never a zero of either sign, and at most 1e26 when
+// |dy| > 1e-6: finite.
+//  * all miss: N and nroy of opposite signs. Then dy has N's sign or is 0
+//    (rl = 0 when its argument overflows), and wherever |dy| > 1e-6, t is a
+//    negative non-zero number or -inf: no hit. (No margin on |dy| is needed:
+//    a sample below the threshold is a miss as well.)
+//  * all hit: N and nroy of the same sign and |dy| > 1e-6 for every sample.
+//    The lower bound: min |N| over the corners times 1 / sqrt(S), S = 1 +
+//    max cx^2 + max cy^2 formed in float64 (products of floats are exact
+//    there), against the kernel's float threshold with a relative margin of
+//    1e-5. What the margin covers: the kernel's two roundings of S
+//    (<= 2^-24 each on S, half of that on rl), v_rsq's 1 ulp (2^-23), the
+//    product's rounding (2^-24) and this bound's own float64 roundings
+//    (~1e-15): under 3e-7 in all, so 30 times over. Then t is positive and
+//    finite: a hit.
+// A hit sample is lit by every light when (one test per call, `lit_ok`,
+// rtmi.cpp uniform_cam): every light has sd.y = -dir.y in (1e-6, 1e6], so its
+// multiplier rcp(sd.y) is a positive number >= 0.99e-6; and
+//   x = fl(fl(bias + fl(dy t + oy)) + ty) > 0.
+// dy t = nroy (1 + e), |e| <= 2 eps (eps = 2^-23: rcp's ulp, the product's
+// half ulp); nroy = -(oy + ty)(1 + e0), |e0| <= eps / 2; so fl(dy t + oy) is
+// -ty within eps (|oy| / 2 + |ty| + 2 |nroy|), adding bias and ty rounds by
+// at most eps (bias + |ty|) / 2 more, and the last rounding keeps the sign:
+// x > 0 when bias > 2 eps (|oy| + |ty| + |nroy|) + eps bias / 2. The test asks
+// for 16 eps (|oy| + |ty| + |nroy|), 8 times that, and bias >= 1e-30; then
+// x >= 7/8 bias and ts = -x rcp(sd.y) is a negative normal number (>= 8e-37 in
+// magnitude): the shadow ray misses the plane. Where the test fails (bias 0,
+// a camera far from the plane, a light below or along the plane) no pixel is
+// uniform-lit; uniform-sky does not depend on it.
+struct UniformCam {
+  int32_t on;      // 0: classify nothing (every lean pixel "mixed")
+  int32_t m;       // samples per pixel side (grid_m)
+  int32_t lit_ok;  // the call's condition for uniform-lit pixels
+  float cam_a, cam_b, cam_c, cam_d, c4, c7, c10, st, of, nroy;
+};
+__host__ __device__ inline int uniform_class(const UniformCam& u, int x, int y) {
+  if (!(fabsf(u.nroy) >= 1e-20f && fabsf(u.nroy) <= 1e20f)) return kUniMixed;
+  float cx[2], cy[2];
+  for (int k = 0; k < 2; ++k) {
+    const float idx = k ? (float)(u.m - 1) : 0.0f;
+    const float px = (float)x + fmaf(idx, u.st, u.of);
+    cx[k] = (px - u.cam_b) * u.cam_a;
+    const float py = (float)y + fmaf(idx, u.st, u.of);
+    cy[k] = (u.cam_d - py) * u.cam_c;
+  }
+  bool pos = true, neg = true, fin = true;
+  float amin = INFINITY;
+  for (int i = 0; i < 2; ++i) {
+    const float ay = fmaf(cx[i], u.c4, -u.c10);
+    for (int j = 0; j < 2; ++j) {
+      const float n = fmaf(cy[j], u.c7, ay);
+      const float a = fabsf(n);
+      pos = pos && n > 0.0f;
+      neg = neg && n < 0.0f;
+      fin = fin && a <= 1e10f;  // (false for a NaN)
+      amin = a < amin ? a : amin;
+    }
+  }
+  if (!fin || !(pos || neg)) return kUniMixed;
+  if (pos != (u.nroy > 0.0f)) return kUniSky;
+  if (!u.lit_ok) return kUniMixed;
+  const double x2 = dmax((double)cx[0] * (double)cx[0], (double)cx[1] * (double)cx[1]);
+  const double y2 = dmax((double)cy[0] * (double)cy[0], (double)cy[1] * (double)cy[1]);
+  const double lo = (double)amin * (1.0 / sqrt(1.0 + x2 + y2)) * (1.0 - 1e-5);
+  return lo > (double)1e-6f ? kUniLit : kUniMixed;
 }
 
 }  // namespace bg

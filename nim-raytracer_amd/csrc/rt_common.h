@@ -266,6 +266,14 @@ struct alignas(16) FLight {
 // light l (l < 8). kPixCount alone: nothing known about the pixel.
 constexpr uint32_t kPixCount = 0x00FFFFFFu;
 
+// Lean list entries of a one-plane launch (rt_frame.hip k_frame_lists,
+// rt_fast.h lean1q_loop): the pixel's group index in the low bits, its
+// uniform class (rt_bins_geom.h kUniMixed / kUniLit / kUniSky) in bits 29-30;
+// -1 is padding. Launches of 2^29 groups or more classify nothing.
+constexpr int kLeanClsShift = 29;
+constexpr int32_t kLeanIdxMask = (1 << kLeanClsShift) - 1;
+enum : int { kUniMixed = 0, kUniLit = 1, kUniSky = 2 };
+
 struct LTri;
 struct FastParams {
   const FObj* objs;

@@ -3475,11 +3475,37 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
   }
   asm volatile("" : "+v"(av.x), "+v"(av.y), "+v"(av.z));
   while (g >= 0) {
-    const int gg = order[g * PPI + lane / LP];  // this lane's pixel (list entry; -1: padding)
+    // this lane's pixel (list entry; -1: padding): its group index below its
+    // uniform class (rt_common.h kLeanClsShift; -1 for padding)
+    const int ge = order[g * PPI + lane / LP];
+    const int gg = ge < 0 ? -1 : ge & kLeanIdxMask;
+    const unsigned long long mixm = bal((ge >> kLeanClsShift) == kUniMixed);
+    const unsigned long long litu = bal((ge >> kLeanClsShift) == kUniLit);
     const unsigned long long vmask = bal(gg >= 0);
     const GroupPix gp = lane_pixel(p, gg >= 0 ? gg : 0);
     const float pxb = (float)gp.x, pyb = (float)gp.y;
     unsigned nlit = 0u, nocc = 0u;
+    F3 r;
+    if (mixm == 0ull) {
+      // No pixel of the item needs its samples: this call's build proved
+      // (rt_bins_geom.h uniform_class, in this loop's own float32 arithmetic)
+      // that every sample of a kUniLit pixel is a camera hit no shadow ray
+      // occludes, and every sample of a kUniSky pixel a miss. The loop below
+      // would add the constant av resp. bg `iters` times from 0 in each
+      // virtual lane and then add equal partial sums pairwise six times (the
+      // virtual-lane stack and the lane tree: 64 virtual lanes per pixel,
+      // whatever LP is): the same operations here, so the same bits. A lit
+      // pixel's samples all count as hits, each with NL shadow rays that hit
+      // nothing; a sky pixel's count as neither.
+      const bool ul = lane_in(litu);
+      const F3 a = f3(ul ? av.x : bg.x, ul ? av.y : bg.y, ul ? av.z : bg.z);
+      r = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+      for (int it = 0; it < iters; ++it) r = f3(r.x + a.x, r.y + a.y, r.z + a.z);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) r = f3(r.x + r.x, r.y + r.y, r.z + r.z);
+      nlit = pc(litu) * (unsigned)V * (unsigned)iters;
+    } else {
     // the binary-counter stack of the V virtual lanes' partial sums, two
     // virtual lanes at a time (two independent sample chains per step; their
     // sum is the tree's first level)
@@ -3583,7 +3609,7 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
     }
     // the pixel's lanes pairwise: xor 1 and 2 by quad permutes (DPP), then
     // xor 4, 8, ... by shuffles
-    F3 r = sum;
+    r = sum;
     r = f3(r.x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r.x), 0xB1, 0xf, 0xf, false)),
            r.y + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r.y), 0xB1, 0xf, 0xf, false)),
            r.z + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r.z), 0xB1, 0xf, 0xf, false)));
@@ -3593,6 +3619,7 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
 #pragma unroll
     for (int off = 4; off < LP; off <<= 1)
       r = f3(r.x + __shfl_xor(r.x, off), r.y + __shfl_xor(r.y, off), r.z + __shfl_xor(r.z, off));
+    }
     if (gg >= 0 && q == 0) {  // renderer.nim:159 (1 / samples.len), :204-209 (the pixel or its block)
       const F3 c = f3(r.x * p->inv_len, r.y * p->inv_len, r.z * p->inv_len);
       if (p->mode == 0 && p->step > 1) {

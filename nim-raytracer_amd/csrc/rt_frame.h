@@ -32,7 +32,10 @@
 //   k_frame_lists    (two-class launches) one block per 16 tiles: its offsets
 //                    summed by the block itself from every earlier tile's
 //                    counts (no inter-block hand-off, no scan launch), its
-//                    pixels written to the lean / general lists in tile order.
+//                    pixels written to the lean / general lists in tile order;
+//                    a one-plane launch's lean pixels with their uniform
+//                    class (rt_bins_geom.h uniform_class: four float32
+//                    corner evaluations per lean pixel).
 // A pixel with more listed faces than its 2^slot_lg slots keeps its true
 // count in the record; the render kernels then traverse the BVH for that
 // pixel's camera rays (the same answers, rt_fast.h mesh_search) — exact, no
@@ -157,6 +160,10 @@ struct RecordsLaunch {
   int32_t* lean;            // capacity ngroups + 64
   int32_t* heavy;           // capacity ngroups
   int32_t* ctr;
+  // uniform classes of the lean pixels (one-plane launches whose lean list
+  // goes to lean1q_loop; uni.on == 0: none), in the lean entries' high bits
+  bg::UniformCam uni;
+  uint32_t* uni_cls;        // per tile row (ntiles x 4): uniform-lit << 16 | uniform-sky entries
 };
 
 struct FrameLaunch {

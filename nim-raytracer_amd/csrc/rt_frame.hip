@@ -371,7 +371,15 @@ __global__ __launch_bounds__(256) void k_frame_lists(const FrameLaunch a) {
     for (int q = 0; q < w; ++q) b += wsum[i][q];
     const int bx = t % a.tiles_x, by = t / a.tiles_x;
     const int g = (by * kTileH + w) * r.ncols + bx * kTileW + lane;
-    if (cls[i] == 1) r.lean[(int)(b >> 32) + (int)lane_rank(ml)] = g;
+    // a lean pixel's uniform class (one-plane launches): into the entry's high bits
+    const int uc = r.uni.on && cls[i] == 1 ? bg::uniform_class(r.uni, px[i].x, px[i].y) : kUniMixed;
+    // the row's counts for rt_scene_last_uniform: a word of its own per tile
+    // row (two counters shared by the launch's 8,100 waves at 1080p cost the
+    // kernel 80 us in same-address atomics)
+    const unsigned long long mul = __ballot(uc == kUniLit), mus = __ballot(uc == kUniSky);
+    if (r.uni.on && lane == 0 && t < a.ntiles)
+      r.uni_cls[t * kTileH + w] = (uint32_t)__popcll(mul) << 16 | (uint32_t)__popcll(mus);
+    if (cls[i] == 1) r.lean[(int)(b >> 32) + (int)lane_rank(ml)] = g | (uc << kLeanClsShift);
     if (cls[i] == 2) r.heavy[(int)(b & 0xffffffffull) + (int)lane_rank(mh)] = g;
     base += wsum[i][0] + wsum[i][1] + wsum[i][2] + wsum[i][3];
   }

@@ -225,6 +225,9 @@ struct rt_scene {
   hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
   bool timed = false;
   int64_t last_lean = 0, last_general = 0;  // rt_scene_last_split
+  // host copies of what the per-call uniform-pixel condition reads (uniform_cam):
+  // every object's FObj.t[1], every light's FLight.v[1]
+  std::vector<float> h_obj_ty, h_light_vy;
   int32_t last_lean_kind = 0;                // rt_scene_last_lean_kernel
   bool stats_kept = true;                    // the last call kept its Stats (no RT_FLAG_NO_STATS)
   // per-wave Stats rows of the last call not yet reduced into acc(): a call
@@ -299,7 +302,8 @@ struct rt_scene {
   struct Frame {                   // per-call buffers of one image size
     int w = 0, h = 0;
     DevBuf<int32_t> cnt, slots, lean, heavy, ctr, orect;
-    DevBuf<uint32_t> info;
+    DevBuf<uint32_t> info, uni_cls;  // uni_cls: per tile row, the uniform classes' counts (RecordsLaunch.uni_cls)
+    int uni_rows = 0;              // its words the last classifying launch wrote
     DevBuf<unsigned long long> omask, status;  // status: per-tile class counts (FrameLaunch.tile_cls)
     DevBuf<HugeFace> huge;
     DevBuf<unsigned char> tiles;   // per skip cell of a tile: shadow skips (k_frame_build1)
@@ -308,6 +312,7 @@ struct rt_scene {
     uint32_t calls = 0;            // build launches (their parity picks the huge-list counter)
     bool counted = false;          // the last launch's lean / general lists were counted on the device
     bool listed = false;           // the last launch built camera-ray lists
+    bool uniform = false;          // the last launch classified its lean pixels (rt_scene_last_uniform)
     hipEvent_t built = nullptr;    // recorded on bstream after this set's builds of a call
     hipEvent_t used = nullptr;     // recorded on the caller's stream at the end of a call that used this set
     bool used_rec = false;         // `used` has been recorded
@@ -316,11 +321,11 @@ struct rt_scene {
     void invalidate() { w = h = 0; }
     size_t bytes() const {
       return cnt.bytes() + slots.bytes() + lean.bytes() + heavy.bytes() + ctr.bytes() + orect.bytes() +
-             info.bytes() + omask.bytes() + status.bytes() + huge.bytes() + tiles.bytes();
+             info.bytes() + uni_cls.bytes() + omask.bytes() + status.bytes() + huge.bytes() + tiles.bytes();
     }
     void release() {
       cnt.release(); slots.release(); lean.release(); heavy.release(); ctr.release(); orect.release();
-      info.release(); omask.release(); status.release(); huge.release(); tiles.release();
+      info.release(); uni_cls.release(); omask.release(); status.release(); huge.release(); tiles.release();
       slot_lg = -1;
       w = h = 0;
     }
@@ -888,6 +893,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<FMesh> fm;
     std::vector<FLight> fl;
     fill_fast_records(d, m, fo, fx, fm, fl);
+    for (const FObj& q : fo) s->h_obj_ty.push_back(q.t[1]);
+    for (const FLight& q : fl) s->h_light_vy.push_back(q.v[1]);
     int rc;
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
         (rc = s->f32.lights.upload(fl)) || (rc = s->f32.normals.upload(n)))
@@ -1487,7 +1494,8 @@ int frame_buffers(rt_scene* s, int w, int h, hipStream_t st) {
   if ((rc = f.cnt.alloc(npx + 1)) || (rc = f.info.alloc(npx)) || (rc = f.lean.alloc(npx + 64)) ||
       (rc = f.heavy.alloc(npx)) || (rc = f.ctr.alloc(FC_WORDS)) ||
       (rc = f.tiles.alloc((size_t)rtmi_frame_skip_cells(w, h))) ||
-      (rc = f.status.alloc((size_t)rtmi_frame_tile_bytes(w, h))))
+      (rc = f.status.alloc((size_t)rtmi_frame_tile_bytes(w, h))) ||
+      (rc = f.uni_cls.alloc((size_t)rtmi_frame_tile_bytes(w, h) * 4)))
     return rc;
   if (s->objbins && ((rc = f.omask.alloc(npx)) || (rc = f.orect.alloc(kObjRectInts)))) return rc;
   if (lists) {
@@ -1509,10 +1517,39 @@ int frame_buffers(rt_scene* s, int w, int h, hipStream_t st) {
   return RT_OK;
 }
 
+// The uniform-pixel proof's inputs (rt_bins_geom.h uniform_class): the
+// float32 values lean1q_loop computes with, and the call's condition for
+// uniform-lit pixels (in float32, as the kernel forms nroy).
+void uniform_cam(const rt_scene* s, const FastParams& p, bg::UniformCam& u) {
+  const int po = p.shadow_mesh == 0 ? 1 : 0;  // the plane (lean1_ok: two objects, one the mesh)
+  const float ty = s->h_obj_ty[(size_t)po], oy = p.cam[1];
+  const float nroy = -(oy + ty);
+  u.on = 1;
+  u.m = p.grid_m;
+  u.cam_a = p.cam_a;
+  u.cam_b = p.cam_b;
+  u.cam_c = p.cam_c;
+  u.cam_d = p.cam_d;
+  u.c4 = p.cam[4];
+  u.c7 = p.cam[7];
+  u.c10 = p.cam[10];
+  u.st = p.sample_step;
+  u.of = p.sample_off;
+  u.nroy = nroy;
+  bool ok = p.bias >= 1e-30f &&
+            (double)p.bias > 16.0 * 1.1920928955078125e-7 *
+                                 ((double)std::fabs(oy) + (double)std::fabs(ty) + (double)std::fabs(nroy));
+  for (int l = 0; l < p.nlight; ++l) {
+    const float sdy = -s->h_light_vy[(size_t)l];
+    ok = ok && sdy > 1e-6f && sdy <= 1e6f;
+  }
+  u.lit_ok = ok ? 1 : 0;
+}
+
 // The call's pixel-record / list parameters (RecordsLaunch) for the
 // launch's pixels.
 void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const FastParams& p, bool records,
-                    bool split, RecordsLaunch& r) {
+                    bool split, bool uniform, RecordsLaunch& r) {
   std::memset(&r, 0, sizeof r);
   r.mode = mp.mode;
   r.y0 = mp.y0;
@@ -1545,6 +1582,10 @@ void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const F
   r.lean = s->fr.lean.p;
   r.heavy = s->fr.heavy.p;
   r.ctr = s->fr.ctr.p;
+  if (split && uniform) {
+    uniform_cam(s, p, r.uni);
+    r.uni_cls = s->fr.uni_cls.p;
+  }
 }
 
 // The mesh's camera-ray lists for the launch's pixels, their records
@@ -1554,7 +1595,7 @@ void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const F
 // traverse the BVH. zero (words, count): the render kernels' queue heads +
 // Stats words, zeroed by the first build launch (*zeroed = true).
 int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastParams& p, bool records, bool split,
-                unsigned int* zero, int nzero, hipStream_t st, bool* ok, bool* zeroed) {
+                bool uniform, unsigned int* zero, int nzero, hipStream_t st, bool* ok, bool* zeroed) {
   *ok = false;
   *zeroed = false;
   if (!s->binnable || s->bin_tris.empty()) return RT_OK;
@@ -1583,7 +1624,7 @@ int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastP
   a.slot_lg = f.slot_lg;
   a.huge = f.huge.p;
   a.parity = (int32_t)(f.calls++ & 1u);
-  records_launch(s, o, mp, p, records, split, a.r);
+  records_launch(s, o, mp, p, records, split, uniform, a.r);
   a.tile_bits = f.tiles.p;
   a.tile_cls = f.status.p;
   static const int diag_b2 = rtmi::diag_env("RTMI_DIAG_B2") ? std::atoi(rtmi::diag_env("RTMI_DIAG_B2")) : 0;
@@ -1599,6 +1640,8 @@ int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastP
     return fail(RT_E_DEVICE, "frame build launch failed: %s", hipGetErrorString((hipError_t)rc));
   }
   f.listed = true;
+  f.uniform = a.r.uni.on != 0;
+  f.uni_rows = a.ntiles * 4;
   *zeroed = zero != nullptr;
   *ok = true;
   return RT_OK;
@@ -1655,6 +1698,8 @@ bool sampler_in_pixel(int32_t aa_kind) {
 // zero / nzero: the render kernels' queue heads + Stats words; a call that
 // builds pixel lists zeroes them in its first build launch (*zeroed), else
 // the caller clears them.
+bool lean1_ok(const rt_scene* s, const rt_options* o, const FastParams& p, unsigned sub);
+
 int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, FastParams& p, int* blocks,
               rt_scene::Order** measuring, hipStream_t st, bool* split, unsigned int* zero, int nzero, bool* zeroed) {
   std::memset(&p, 0, sizeof p);
@@ -1806,7 +1851,12 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
     }
     return RT_OK;
   };
-  if ((rc = frame_build(s, o, mp, p, records, *split, zero, nzero, bs, &lists, zeroed))) {
+  // the lean pixels' uniform classes: when the lean list goes to lean1q_loop
+  // (launch() below takes the same decisions), off with RT_FLAG_NO_UNIFORM;
+  // the class sits above the group index in a list entry
+  const bool uniform = *split && lean1_ok(s, o, p, sub) && !(o->flags & (RT_FLAG_NO_LEAN1 | RT_FLAG_NO_UNIFORM)) &&
+                       rtmi_lean1_quads() && (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
+  if ((rc = frame_build(s, o, mp, p, records, *split, uniform, zero, nzero, bs, &lists, zeroed))) {
     join();
     return rc;
   }
@@ -1943,6 +1993,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
   // when it returns early or runs the float64 kernel
   s->fr.counted = false;
   s->fr.listed = false;
+  s->fr.uniform = false;
   s->pending_reduce = 0;
   s->last_lean = 0;
   s->last_lean_kind = 0;
@@ -1978,7 +2029,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
       FastParams pf;
       std::memset(&pf, 0, sizeof pf);
       bool zeroed = false;
-      if (int rc = frame_build(s, o, mp, pf, true, false, nullptr, 0, st, &lists, &zeroed)) return rc;
+      if (int rc = frame_build(s, o, mp, pf, true, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
       if (lists) p.pix_info = s->fr.info.p;
     }
     // one pixel per wave (k_render_px64): akGrid with >= 64 samples per
@@ -2474,6 +2525,23 @@ extern "C" int rt_scene_last_split(rt_scene* s, int64_t* lean_groups, int64_t* g
   if (!s || !lean_groups || !general_groups) return fail(RT_E_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
   return last_lists(s, lean_groups, general_groups);
+}
+
+extern "C" int rt_scene_last_uniform(rt_scene* s, int32_t* lit, int32_t* sky) {
+  if (!s || !lit || !sky) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  *lit = 0;
+  *sky = 0;
+  if (!s->fr.counted || !s->fr.uniform) return RT_OK;
+  DeviceGuard g(s->device);
+  std::vector<uint32_t> c((size_t)s->fr.uni_rows);
+  HIP_TRY(hipEventSynchronize(s->done));
+  HIP_TRY(hipMemcpy(c.data(), s->fr.uni_cls.p, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (const uint32_t v : c) {
+    *lit += (int32_t)(v >> 16);
+    *sky += (int32_t)(v & 0xffffu);
+  }
+  return RT_OK;
 }
 
 extern "C" int rt_scene_last_lean_kernel(rt_scene* s, int32_t* kind) {

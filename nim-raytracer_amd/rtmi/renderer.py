@@ -126,6 +126,13 @@ class DeviceScene:
         check(lib().rt_scene_last_split(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def last_uniform(self):
+        """(lit, sky): the last call's lean pixels proved uniform-lit and
+        uniform-sky by its build (0, 0 when it classified nothing)."""
+        a, b = C.c_int32(), C.c_int32()
+        check(lib().rt_scene_last_uniform(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def last_lean_kernel(self):
         """Kernels of the last call's two classes: bits 0-1 the lean pixels'
         (0 none, 1 k_render_lean, 2 k_render_lean1, 3 merged), bits 2-3 the

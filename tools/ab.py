@@ -16,7 +16,15 @@ from rtmi.scene import Antialias, Options, Precision, akGrid, flatten  # noqa: E
 
 
 def load(path):
-    return abi.bind(C.CDLL(path))
+    """Binds what the library exports: an older build (the parent of an A/B)
+    may lack the newest rtmi.h symbols, which this tool does not call."""
+    lib = C.CDLL(path)
+    for name, (res, args) in abi.SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+    return lib
 
 
 def variants():
@@ -60,7 +68,7 @@ def main():
     L = [load(p) for p in libs]
     for lib in L:
         assert lib.rt_init(0) == 0, lib.rt_last_error()
-    res = {}
+    res, all_reps = {}, {}
     stream = torch.cuda.current_stream()
     for name, (scene, opts) in variants().items():
         flat = flatten(scene)
@@ -101,7 +109,10 @@ def main():
         for lib, h in zip(L, hs):
             lib.rt_scene_destroy(h)
         res[name] = {os.path.basename(p): round(min(t), 3) for p, t in times.items()}
+        all_reps[name] = {os.path.basename(p): [round(x, 4) for x in t] for p, t in times.items()}
         print(name, res[name], flush=True)
+        print(name, "reps", all_reps[name], flush=True)  # rep r of every library ran back to back: a pair
+    res["_reps"] = all_reps
     json.dump(res, open("gpurun_out/ab.json", "w"), indent=1)
 
 
