@@ -234,6 +234,14 @@ typedef struct rt_options {
  * running its sample loop. The image and Stats are the same, bit for bit
  * (tests/test_gpu_uniform.py). */
 #define RT_FLAG_NO_UNIFORM 0x8000u
+/* One-plane two-class launches: do not tag ground pixels. By default the
+ * per-call build tags the general pixels that have an empty camera-ray list
+ * and pass the uniform-lit proof above (flat ground in the mesh's shadow):
+ * every sample hits the plane and only its shadow rays can meet the mesh, so
+ * the batched kernel gives them a sample loop of their own (the shadow
+ * searches alone). The image and Stats are the same, bit for bit
+ * (tests/test_gpu_ground.py). */
+#define RT_FLAG_NO_GROUND1 0x10000u
 
 /* Stats (src/renderer/stats.nim:4-13) plus ray counts for Mray/s. */
 typedef struct rt_stats {
@@ -510,6 +518,12 @@ int rt_scene_last_lean_kernel(rt_scene *scene, int32_t *kind);
  * classified nothing (RT_FLAG_NO_UNIFORM, not a one-plane two-class launch).
  * Waits for the call. */
 int rt_scene_last_uniform(rt_scene *scene, int32_t *lit, int32_t *sky);
+/* Of the last render call's general pixel groups (rt_scene_last_split and
+ * rt_scene_last_batch count them all): how many the per-call build tagged as
+ * ground pixels. 0 when the call tagged nothing (RT_FLAG_NO_GROUND1, not a
+ * one-plane two-class launch with the one-plane batched kernel). Waits for
+ * the call. */
+int rt_scene_last_ground(rt_scene *scene, int32_t *ground);
 
 /* ---- helpers ----------------------------------------------------------- */
 

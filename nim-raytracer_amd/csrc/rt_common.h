@@ -273,6 +273,12 @@ constexpr uint32_t kPixCount = 0x00FFFFFFu;
 constexpr int kLeanClsShift = 29;
 constexpr int32_t kLeanIdxMask = (1 << kLeanClsShift) - 1;
 enum : int { kUniMixed = 0, kUniLit = 1, kUniSky = 2 };
+// General list entries of a one-plane launch whose general list goes to
+// gen1_loop (rtmi.cpp fill_fast): bit 29 set for a ground pixel — an empty
+// camera list and the uniform-lit proof, so every sample hits the plane and
+// only its shadow rays can meet the mesh (rt_fast.h ground1_batch). Every
+// other launch's general list holds plain group indices.
+constexpr int32_t kGenGroundBit = 1 << kLeanClsShift;
 
 struct LTri;
 struct FastParams {

@@ -2565,6 +2565,159 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
   return true;
 }
 
+// gen1_batch for a ground pixel (rt_common.h kGenGroundBit: an empty camera
+// list, and this call's build proved the pixel uniform-lit, rt_bins_geom.h
+// uniform_class): every camera ray hits the plane at a positive finite t,
+// the normal is (0, 1, 0), no shadow ray meets the plane (its t is a negative
+// number: lit_ok), so a sample's colour depends on one bit per light whose
+// skip bit is clear — whether its shadow ray meets the mesh. What is left of
+// gen1_batch per sample: d, th and the shadow origin in its expressions (the
+// FMAs with N = (0, 1, 0) included: every later bit depends on them), and
+// per unskipped light the mesh gate, the cell and the cell loop (stop = the
+// float below +inf either way round the two objects, the plane's t being
+// negative). No camera select chain, hit masks, face normals, plane shadow
+// test or albedo select; a skipped light costs its irradiance term. The
+// same irr_add chain in light order, mul3 and acc_add3 in sample order, the
+// same Stats (every sample a hit with NL shadow rays, + the occluded pairs)
+// and the same fallback (false before anything is added). Frames and Stats
+// bit-identical to gen1_batch (tests/test_gpu_ground.py, RT_FLAG_NO_GROUND1).
+// S = RTMI_GROUND_BATCH samples per lane: 4 = the whole 256-sample pixel at
+// once (iters % 4 == 0, rtmi.cpp lean1_ok), so a light cell the pixel's
+// samples share is searched once for all of them.
+#ifndef RTMI_GROUND_BATCH
+#define RTMI_GROUND_BATCH 4
+#endif
+constexpr int kGroundBatch = RTMI_GROUND_BATCH;
+static_assert(kGroundBatch == 1 || kGroundBatch == 2 || kGroundBatch == 4, "iters is a multiple of 4");
+template <int S, int NL>
+__device__ __forceinline__ bool ground1_batch(KP p, const GroupPix& gp, int it0, unsigned pinfo, Acc& acc,
+                                              Stats32& wi) {
+  p = params();
+  const int mesh = p->shadow_mesh, po = 1 - mesh;
+  const FObj mob = at(p->objs, mesh);
+  F3 ro[S];  // the shadow origins in the mesh's frame (the same for every light)
+  {
+    const F3 o = f3(p->cam[0], p->cam[1], p->cam[2]);
+    const float nroy = -(o.y + at(p->objs, po).t[1]), bias = p->bias;
+    const int mm = p->grid_m - 1, lg = p->log2_grid_m;
+    const float st = p->sample_step, of = p->sample_off;
+    const float px = (float)gp.x + __builtin_fmaf((float)(gp.sub & mm), st, of);
+    const float cx = (px - p->cam_b) * p->cam_a;
+    const float q0 = __builtin_fmaf(cx, cx, 1.0f);
+    const float ax = __builtin_fmaf(cx, p->cam[3], -p->cam[9]), ay = __builtin_fmaf(cx, p->cam[4], -p->cam[10]),
+                az = __builtin_fmaf(cx, p->cam[5], -p->cam[11]);
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const int s = (it0 + k) * 64 + gp.sub;
+      const float py = (float)gp.y + __builtin_fmaf((float)(s >> lg), st, of);
+      const float cy = (p->cam_d - py) * p->cam_c;
+      const float rl = rsq(__builtin_fmaf(cy, cy, q0));
+      const F3 d = f3(__builtin_fmaf(cy, p->cam[6], ax) * rl, __builtin_fmaf(cy, p->cam[7], ay) * rl,
+                      __builtin_fmaf(cy, p->cam[8], az) * rl);
+      const float th = nroy * rcp(d.y);
+      const F3 hw = f3(__builtin_fmaf(d.x, th, o.x), __builtin_fmaf(d.y, th, o.y), __builtin_fmaf(d.z, th, o.z));
+      const F3 so = f3(__builtin_fmaf(0.0f, bias, hw.x), __builtin_fmaf(1.0f, bias, hw.y),
+                       __builtin_fmaf(0.0f, bias, hw.z));
+      ro[k] = f3(so.x + mob.t[0], so.y + mob.t[1], so.z + mob.t[2]);
+    }
+  }
+  // per light and sample: the lanes whose shadow ray meets the mesh
+  unsigned long long occ[NL][S];
+  unsigned nocc = 0u;
+  const unsigned skipw = pinfo >> 24;
+#pragma unroll
+  for (int li = 0; li < NL; ++li) {
+#pragma unroll
+    for (int k = 0; k < S; ++k) occ[li][k] = 0ull;
+    if (((skipw >> li) & 1u) != 0u || mob.root < 0) continue;
+    p = params();
+    const FLight L = at(p->lights, li);
+    const F3 sd = f3(-L.v[0], -L.v[1], -L.v[2]);
+    unsigned long long pm[S], anyp = 0ull;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      pm[k] = bal(mesh_gate(mob, slab_ray(ro[k], sd)));
+      anyp |= pm[k];
+    }
+    if (anyp == 0ull) continue;
+    const KP q = params();
+    if (!q->grids || q->grids[li].gu <= 0) return false;
+    const RT_CONST LightGrid& G = cp(q->grids)[li];
+    F3 rd[S];
+    float stop[S], tc[S], best[S];
+    unsigned long long unused[S];
+    int cell[S];
+    unsigned long long todo[S], left = 0ull, unsafe = 0ull;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const bool part = lane_in(pm[k]);
+      rd[k] = sd;
+      stop[k] = __uint_as_float(__float_as_uint(finf()) - 1u);
+      tc[k] = part ? finf() : -1.0f;
+      best[k] = part ? finf() : 0.0f;
+      unused[k] = 0ull;
+      const F3 r = ro[k];
+      const float gu = __builtin_fmaf(r.x, G.e1[0], __builtin_fmaf(r.y, G.e1[1], r.z * G.e1[2]));
+      const float gv = __builtin_fmaf(r.x, G.e2[0], __builtin_fmaf(r.y, G.e2[1], r.z * G.e2[2]));
+      const float fu = (gu - G.u0) * G.inv_h, fv = (gv - G.v0) * G.inv_h;
+      const bool safe = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fabsf(r.z)) <= G.rmax;
+      const bool on = fu >= 0.0f && fu < (float)G.gu && fv >= 0.0f && fv < (float)G.gv;
+      cell[k] = safe && on ? G.off_base + (int)fv * G.gu + (int)fu : -1;
+      todo[k] = bal(part && cell[k] >= 0);
+      unsafe |= bal(part && !safe);
+      left |= todo[k];
+    }
+    if (unsafe != 0ull) return false;
+    const int32_t* bent = q->grid_ent + G.ent_base;
+    while (left != 0ull) {  // gen1_batch's cell loop
+      int kb = -1;
+#pragma unroll
+      for (int k = S - 1; k >= 0; --k)
+        if (todo[k]) kb = __builtin_amdgcn_readlane(cell[k], (int)__builtin_ctzll(todo[k]));
+      unsigned fl = 0u;
+      unsigned long long own[S];
+      left = 0ull;
+#pragma unroll
+      for (int k = 0; k < S; ++k) {
+        own[k] = bal(cell[k] == kb) & todo[k];
+        todo[k] &= ~own[k];
+        left |= todo[k];
+        fl |= own[k] != 0ull ? (1u << k) : 0u;
+      }
+      (void)list_search_batch<S, false>(q, bent, cp(q->grid_off)[kb], cp(q->grid_off)[kb + 1], fl, ro, rd, stop, own,
+                                        unused, best, tc, nullptr, grid_rec_of(q, li, G));
+    }
+#pragma unroll
+    for (int k = 0; k < S; ++k) {  // found => 0 <= t < inf: the hit counts
+      occ[li][k] = pm[k] & bal(__float_as_uint(best[k]) != __float_as_uint(finf()));
+      nocc += pc(occ[li][k]);
+    }
+  }
+  // the samples' colours in order: the plane's albedo / pi x E
+  p = params();
+  F3 E[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) E[k] = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+  for (int li = 0; li < NL; ++li) {
+    const FLight L = at(p->lights, li);
+    const float ndl = fmaxf(dot3(f3(0.0f, 1.0f, 0.0f), f3(-L.v[0], -L.v[1], -L.v[2])), 0.0f);
+#pragma unroll
+    for (int k = 0; k < S; ++k) irr_add(E[k], L.ci, lane_in(occ[li][k]) ? 0.0f : ndl);
+  }
+  const RT_CONST FObjX& px_ = at(p->objx, po);
+  const F3 ap = f3(px_.albedo_pi[0], px_.albedo_pi[1], px_.albedo_pi[2]);
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const F3 a = mul3(ap, E[k]);
+    acc_add3(acc, a.x, a.y, a.z);
+  }
+  wi.v[STAT_PRIMARY] += (unsigned)(64 * S);
+  wi.v[STAT_SHADOW] += (unsigned)(NL * 64 * S);
+  wi.v[STAT_HITS] += (unsigned)(64 * S) + nocc;
+  return true;
+}
+
 // multiJittered / correlatedMultiJittered (sampling.nim:39-113): the wave
 // builds each of its pixels' (m, m) tables in LDS — canonical entries spread
 // over the pixel's lanes, then the x shuffle with one lane per column and
@@ -3781,7 +3934,18 @@ __device__ __forceinline__ void gen1_loop(KP p, LdsF* ls, Stats32& ws, unsigned 
   while (g >= 0) {
     p = params();
     const int iters = p->iters;
-    const int gg = cp(p->order)[g];
+    // the list entry: the pixel's group index, below the ground tag where
+    // this call's build wrote one (rt_common.h kGenGroundBit; a launch of
+    // 2^29 groups or more holds plain indices)
+    const int ge = cp(p->order)[g];
+    const bool gnd = (ge & kGenGroundBit) != 0 && p->ngroups <= kLeanIdxMask;
+    const int gg = gnd ? ge & kLeanIdxMask : ge;
+#ifdef RTMI_DIAG_NOGROUND
+    if (gnd) {  // diagnostic build only (wrong images): what the ground pixels cost
+      g = wq.next();
+      continue;
+    }
+#endif
     GroupPix gp = group_pixel(p, gg, lane_id_fresh());
     gp.valid = true;  // the lists hold only pixels of the launch (rtmi.cpp split_lists)
     // a one-pixel group: its placement is wave-uniform (scalar registers;
@@ -3801,7 +3965,11 @@ __device__ __forceinline__ void gen1_loop(KP p, LdsF* ls, Stats32& ws, unsigned 
     // a pixel list past its slots (rt_frame.h): the one-sample loop, whose
     // camera rays take the BVH for this pixel
     bool ok = (pinfo & kPixCount) <= (1u << p->slot_lg);
-    for (int it = 0; ok && it < iters; it += kGenBatch) ok = gen1_batch<kGenBatch, NL>(p, gp, pu, it, pinfo, acc, wi);
+    if (gnd) {
+      for (int it = 0; ok && it < iters; it += kGroundBatch) ok = ground1_batch<kGroundBatch, NL>(p, gp, it, pinfo, acc, wi);
+    } else {
+      for (int it = 0; ok && it < iters; it += kGenBatch) ok = gen1_batch<kGenBatch, NL>(p, gp, pu, it, pinfo, acc, wi);
+    }
     if (params()->flags & RT_DEV_FLAG_FALLBACK) ok = false;  // test hook (RT_FLAG_BATCH_FALLBACK)
     if (ok) {
       ws.v[STAT_PRIMARY] += wi.v[STAT_PRIMARY];

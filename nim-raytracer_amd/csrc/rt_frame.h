@@ -35,7 +35,9 @@
 //                    pixels written to the lean / general lists in tile order;
 //                    a one-plane launch's lean pixels with their uniform
 //                    class (rt_bins_geom.h uniform_class: four float32
-//                    corner evaluations per lean pixel).
+//                    corner evaluations per lean pixel), and its general
+//                    pixels with an empty camera list that the same proof
+//                    finds uniform-lit tagged as ground pixels.
 // A pixel with more listed faces than its 2^slot_lg slots keeps its true
 // count in the record; the render kernels then traverse the BVH for that
 // pixel's camera rays (the same answers, rt_fast.h mesh_search) — exact, no
@@ -163,7 +165,13 @@ struct RecordsLaunch {
   // uniform classes of the lean pixels (one-plane launches whose lean list
   // goes to lean1q_loop; uni.on == 0: none), in the lean entries' high bits
   bg::UniformCam uni;
-  uint32_t* uni_cls;        // per tile row (ntiles x 4): uniform-lit << 16 | uniform-sky entries
+  // ground pixels of the general list (one-plane launches whose general list
+  // goes to gen1_loop; 0: none): general pixels with an empty camera list
+  // that the same proof (uni, filled whenever either class is on) finds
+  // uniform-lit, tagged with kGenGroundBit
+  int32_t ground;
+  // per tile row (ntiles x 4): uniform-lit << 16 | ground << 8 | uniform-sky entries
+  uint32_t* uni_cls;
 };
 
 struct FrameLaunch {

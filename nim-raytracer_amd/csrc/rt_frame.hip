@@ -372,15 +372,20 @@ __global__ __launch_bounds__(256) void k_frame_lists(const FrameLaunch a) {
     const int bx = t % a.tiles_x, by = t / a.tiles_x;
     const int g = (by * kTileH + w) * r.ncols + bx * kTileW + lane;
     // a lean pixel's uniform class (one-plane launches): into the entry's high bits
-    const int uc = r.uni.on && cls[i] == 1 ? bg::uniform_class(r.uni, px[i].x, px[i].y) : kUniMixed;
-    // the row's counts for rt_scene_last_uniform: a word of its own per tile
-    // row (two counters shared by the launch's 8,100 waves at 1080p cost the
-    // kernel 80 us in same-address atomics)
-    const unsigned long long mul = __ballot(uc == kUniLit), mus = __ballot(uc == kUniSky);
-    if (r.uni.on && lane == 0 && t < a.ntiles)
-      r.uni_cls[t * kTileH + w] = (uint32_t)__popcll(mul) << 16 | (uint32_t)__popcll(mus);
+    // a general pixel with an empty camera list (gen1_loop launches): the
+    // same proof, uniform-lit = a ground pixel, tagged in the entry's high bits
+    const bool lean_c = r.uni.on && cls[i] == 1, gen_c = r.ground && cls[i] == 2 && (inf[i] & kPixCount) == 0u;
+    const int uc = lean_c || gen_c ? bg::uniform_class(r.uni, px[i].x, px[i].y) : kUniMixed;
+    const bool gnd = gen_c && uc == kUniLit;
+    // the row's counts for rt_scene_last_uniform / _last_ground: a word of
+    // its own per tile row (two counters shared by the launch's 8,100 waves
+    // at 1080p cost the kernel 80 us in same-address atomics)
+    const unsigned long long mul = __ballot(lean_c && uc == kUniLit), mus = __ballot(lean_c && uc == kUniSky);
+    const unsigned long long mug = __ballot(gnd);
+    if ((r.uni.on || r.ground) && lane == 0 && t < a.ntiles)
+      r.uni_cls[t * kTileH + w] = (uint32_t)__popcll(mul) << 16 | (uint32_t)__popcll(mug) << 8 | (uint32_t)__popcll(mus);
     if (cls[i] == 1) r.lean[(int)(b >> 32) + (int)lane_rank(ml)] = g | (uc << kLeanClsShift);
-    if (cls[i] == 2) r.heavy[(int)(b & 0xffffffffull) + (int)lane_rank(mh)] = g;
+    if (cls[i] == 2) r.heavy[(int)(b & 0xffffffffull) + (int)lane_rank(mh)] = gnd ? g | kGenGroundBit : g;
     base += wsum[i][0] + wsum[i][1] + wsum[i][2] + wsum[i][3];
   }
   if ((int)blockIdx.x == (int)gridDim.x - 1) {  // the last chunk: the list lengths, the lean list's -1 padding

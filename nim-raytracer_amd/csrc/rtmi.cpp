@@ -313,6 +313,7 @@ struct rt_scene {
     bool counted = false;          // the last launch's lean / general lists were counted on the device
     bool listed = false;           // the last launch built camera-ray lists
     bool uniform = false;          // the last launch classified its lean pixels (rt_scene_last_uniform)
+    bool ground = false;           // the last launch tagged its ground pixels (rt_scene_last_ground)
     hipEvent_t built = nullptr;    // recorded on bstream after this set's builds of a call
     hipEvent_t used = nullptr;     // recorded on the caller's stream at the end of a call that used this set
     bool used_rec = false;         // `used` has been recorded
@@ -1549,7 +1550,7 @@ void uniform_cam(const rt_scene* s, const FastParams& p, bg::UniformCam& u) {
 // The call's pixel-record / list parameters (RecordsLaunch) for the
 // launch's pixels.
 void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const FastParams& p, bool records,
-                    bool split, bool uniform, RecordsLaunch& r) {
+                    bool split, bool uniform, bool ground, RecordsLaunch& r) {
   std::memset(&r, 0, sizeof r);
   r.mode = mp.mode;
   r.y0 = mp.y0;
@@ -1582,8 +1583,10 @@ void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const F
   r.lean = s->fr.lean.p;
   r.heavy = s->fr.heavy.p;
   r.ctr = s->fr.ctr.p;
-  if (split && uniform) {
+  if (split && (uniform || ground)) {  // one proof for both classes
     uniform_cam(s, p, r.uni);
+    r.uni.on = uniform ? 1 : 0;
+    r.ground = ground ? 1 : 0;
     r.uni_cls = s->fr.uni_cls.p;
   }
 }
@@ -1595,7 +1598,7 @@ void records_launch(rt_scene* s, const rt_options* o, const Mapping& mp, const F
 // traverse the BVH. zero (words, count): the render kernels' queue heads +
 // Stats words, zeroed by the first build launch (*zeroed = true).
 int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastParams& p, bool records, bool split,
-                bool uniform, unsigned int* zero, int nzero, hipStream_t st, bool* ok, bool* zeroed) {
+                bool uniform, bool ground, unsigned int* zero, int nzero, hipStream_t st, bool* ok, bool* zeroed) {
   *ok = false;
   *zeroed = false;
   if (!s->binnable || s->bin_tris.empty()) return RT_OK;
@@ -1624,7 +1627,7 @@ int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastP
   a.slot_lg = f.slot_lg;
   a.huge = f.huge.p;
   a.parity = (int32_t)(f.calls++ & 1u);
-  records_launch(s, o, mp, p, records, split, uniform, a.r);
+  records_launch(s, o, mp, p, records, split, uniform, ground, a.r);
   a.tile_bits = f.tiles.p;
   a.tile_cls = f.status.p;
   static const int diag_b2 = rtmi::diag_env("RTMI_DIAG_B2") ? std::atoi(rtmi::diag_env("RTMI_DIAG_B2")) : 0;
@@ -1641,6 +1644,7 @@ int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastP
   }
   f.listed = true;
   f.uniform = a.r.uni.on != 0;
+  f.ground = a.r.ground != 0;
   f.uni_rows = a.ntiles * 4;
   *zeroed = zero != nullptr;
   *ok = true;
@@ -1856,7 +1860,13 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   // the class sits above the group index in a list entry
   const bool uniform = *split && lean1_ok(s, o, p, sub) && !(o->flags & (RT_FLAG_NO_LEAN1 | RT_FLAG_NO_UNIFORM)) &&
                        rtmi_lean1_quads() && (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
-  if ((rc = frame_build(s, o, mp, p, records, *split, uniform, zero, nzero, bs, &lists, zeroed))) {
+  // the general pixels' ground class: when the general list goes to
+  // gen1_loop (launch() below: gen1), off with RT_FLAG_NO_GROUND1
+  const bool ground = *split && lean1_ok(s, o, p, sub) &&
+                      !(o->flags & (RT_FLAG_NO_BATCH | RT_FLAG_NO_GEN1 | RT_FLAG_NO_GROUND1)) && p.grids &&
+                      rtmi_gen_f32_blocks_per_cu(sub, f32_table_lds(s, o)) > 0 &&
+                      (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
+  if ((rc = frame_build(s, o, mp, p, records, *split, uniform, ground, zero, nzero, bs, &lists, zeroed))) {
     join();
     return rc;
   }
@@ -1994,6 +2004,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
   s->fr.counted = false;
   s->fr.listed = false;
   s->fr.uniform = false;
+  s->fr.ground = false;
   s->pending_reduce = 0;
   s->last_lean = 0;
   s->last_lean_kind = 0;
@@ -2029,7 +2040,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
       FastParams pf;
       std::memset(&pf, 0, sizeof pf);
       bool zeroed = false;
-      if (int rc = frame_build(s, o, mp, pf, true, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
+      if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
       if (lists) p.pix_info = s->fr.info.p;
     }
     // one pixel per wave (k_render_px64): akGrid with >= 64 samples per
@@ -2539,8 +2550,21 @@ extern "C" int rt_scene_last_uniform(rt_scene* s, int32_t* lit, int32_t* sky) {
   HIP_TRY(hipMemcpy(c.data(), s->fr.uni_cls.p, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (const uint32_t v : c) {
     *lit += (int32_t)(v >> 16);
-    *sky += (int32_t)(v & 0xffffu);
+    *sky += (int32_t)(v & 0xffu);
   }
+  return RT_OK;
+}
+
+extern "C" int rt_scene_last_ground(rt_scene* s, int32_t* ground) {
+  if (!s || !ground) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  *ground = 0;
+  if (!s->fr.counted || !s->fr.ground) return RT_OK;
+  DeviceGuard g(s->device);
+  std::vector<uint32_t> c((size_t)s->fr.uni_rows);
+  HIP_TRY(hipEventSynchronize(s->done));
+  HIP_TRY(hipMemcpy(c.data(), s->fr.uni_cls.p, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (const uint32_t v : c) *ground += (int32_t)((v >> 8) & 0xffu);
   return RT_OK;
 }
 

@@ -34,6 +34,7 @@ RT_FLAG_NO_OBJ_BATCH = 0x1000
 RT_FLAG_COMPACT = 0x2000
 RT_FLAG_F64_PER_LANE = 0x4000
 RT_FLAG_NO_UNIFORM = 0x8000
+RT_FLAG_NO_GROUND1 = 0x10000
 RT_BVH_SAH = 0
 RT_OBJ_SLASH_INDICES = 0x1
 RT_BVH_PLOC = 1
@@ -187,6 +188,7 @@ SIGNATURES = {
     "rt_scene_last_lean_kernel": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "rt_scene_last_batch": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rt_scene_last_uniform": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rt_scene_last_ground": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "rt_mat4_inverse": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_load_geom": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "rt_ppm_encode_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -133,6 +133,13 @@ class DeviceScene:
         check(lib().rt_scene_last_uniform(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def last_ground(self):
+        """The last call's general pixels its build tagged as ground pixels
+        (0 when it tagged nothing)."""
+        a = C.c_int32()
+        check(lib().rt_scene_last_ground(self.h, C.byref(a)))
+        return int(a.value)
+
     def last_lean_kernel(self):
         """Kernels of the last call's two classes: bits 0-1 the lean pixels'
         (0 none, 1 k_render_lean, 2 k_render_lean1, 3 merged), bits 2-3 the

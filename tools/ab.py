@@ -1,6 +1,11 @@
 """In-process A/B timing of several librtmi.so builds (interleaved reps).
 
     RTMI_LIBS=path/a.so,path/b.so ABLATE=c3_full,ground_nolights python tools/ab.py
+
+REPS interleaved reps are recorded after WARMUP (default 0) unrecorded ones of
+the same shape: the first two or three reps of a process run 5-10 % slower
+for every library alike while the clocks settle, which is no part of a
+library's run-to-run spread.
 """
 import ctypes as C
 import json
@@ -65,6 +70,7 @@ def variants():
 def main():
     libs = os.environ["RTMI_LIBS"].split(",")
     reps = int(os.environ.get("REPS", "4"))
+    warm = int(os.environ.get("WARMUP", "0"))
     L = [load(p) for p in libs]
     for lib in L:
         assert lib.rt_init(0) == 0, lib.rt_last_error()
@@ -93,7 +99,7 @@ def main():
             print(f"  {os.path.basename(p)}: stats=({st.num_primary_rays},{st.num_intersection_tests},"
                   f"{st.num_intersection_hits},{st.num_shadow_rays},{st.num_reflection_rays}) "
                   f"maxdiff={d.max().item():.3g} frac>2e-3={(d > 2e-3).float().mean().item():.2e}", flush=True)
-        for r in range(reps):
+        for r in range(-warm, reps):
             for p, lib, h in zip(libs, L, hs):
                 st = abi.rt_stats()
                 lib.rt_render_lines_device(h, C.byref(o), C.c_void_p(fb.data_ptr()), 0, opts.height, 1, 1,
@@ -105,7 +111,8 @@ def main():
                                                C.c_void_p(stream.cuda_stream or None), None)
                 e1.record(stream)
                 torch.cuda.synchronize()
-                times[p].append(e0.elapsed_time(e1) / 3)
+                if r >= 0:
+                    times[p].append(e0.elapsed_time(e1) / 3)
         for lib, h in zip(L, hs):
             lib.rt_scene_destroy(h)
         res[name] = {os.path.basename(p): round(min(t), 3) for p, t in times.items()}
