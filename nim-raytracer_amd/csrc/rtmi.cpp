@@ -1521,9 +1521,9 @@ int frame_buffers(rt_scene* s, int w, int h, hipStream_t st) {
 // The uniform-pixel proof's inputs (rt_bins_geom.h uniform_class): the
 // float32 values lean1q_loop computes with, and the call's condition for
 // uniform-lit pixels (in float32, as the kernel forms nroy).
-void uniform_cam(const rt_scene* s, const FastParams& p, bg::UniformCam& u) {
-  const int po = p.shadow_mesh == 0 ? 1 : 0;  // the plane (lean1_ok: two objects, one the mesh)
-  const float ty = s->h_obj_ty[(size_t)po], oy = p.cam[1];
+// ty: the plane's FObj::t[1]; light_vy: every light's FLight::v[1].
+void uniform_cam(float ty, const float* light_vy, const FastParams& p, bg::UniformCam& u) {
+  const float oy = p.cam[1];
   const float nroy = -(oy + ty);
   u.on = 1;
   u.m = p.grid_m;
@@ -1541,10 +1541,14 @@ void uniform_cam(const rt_scene* s, const FastParams& p, bg::UniformCam& u) {
             (double)p.bias > 16.0 * 1.1920928955078125e-7 *
                                  ((double)std::fabs(oy) + (double)std::fabs(ty) + (double)std::fabs(nroy));
   for (int l = 0; l < p.nlight; ++l) {
-    const float sdy = -s->h_light_vy[(size_t)l];
+    const float sdy = -light_vy[l];
     ok = ok && sdy > 1e-6f && sdy <= 1e6f;
   }
   u.lit_ok = ok ? 1 : 0;
+}
+void uniform_cam(const rt_scene* s, const FastParams& p, bg::UniformCam& u) {
+  const int po = p.shadow_mesh == 0 ? 1 : 0;  // the plane (lean1_ok: two objects, one the mesh)
+  uniform_cam(s->h_obj_ty[(size_t)po], s->h_light_vy.data(), p, u);
 }
 
 // The call's pixel-record / list parameters (RecordsLaunch) for the
@@ -1704,6 +1708,39 @@ bool sampler_in_pixel(int32_t aa_kind) {
 // the caller clears them.
 bool lean1_ok(const rt_scene* s, const rt_options* o, const FastParams& p, unsigned sub);
 
+// The camera, sample-grid and bias words of FastParams: what every float32
+// kernel forms its camera rays from, and all the uniform-pixel proof reads of
+// a call (uniform_cam; the test hook rtmi_test_uniform forms them here too).
+void fast_camera(const double* c2w, double fov, const rt_options* o, FastParams& p) {
+  // camera: origin = C2W * (0,0,0,1) = column 3; dir = C2W * normalize(cx, cy, -1, 0)
+  for (int k = 0; k < 3; ++k) {
+    p.cam[k] = (float)c2w[12 + k];
+    p.cam[3 + k] = (float)c2w[0 + k];
+    p.cam[6 + k] = (float)c2w[4 + k];
+    p.cam[9 + k] = (float)c2w[8 + k];
+  }
+  const double f = std::tan(fov * (3.14159265358979323846 / 180.0) / 2);
+  const double r = (double)o->width / (double)o->height;
+  p.cam_a = (float)(2.0 * r * f / (double)o->width);  // cx = ((2 x r)/w - r) f = (x - w/2) 2rf/w
+  p.cam_b = (float)(0.5 * (double)o->width);
+  p.cam_c = (float)(2.0 * f / (double)o->height);     // cy = (1 - 2y/h) f = (h/2 - y) 2f/h
+  p.cam_d = (float)(0.5 * (double)o->height);
+  p.bias = (float)o->bias;
+  const int m = o->aa_kind != RT_AA_NONE ? o->grid_size : 1;
+  const int spp = m * m;
+  p.inv_len = (float)(1.0 / (double)spp);
+  p.sample_step = (float)(1.0 / (double)m);
+  p.sample_off = (float)(1.0 / (double)m * 0.5);
+  p.log2_grid_m = -1;
+  for (int k = 0; k <= 12; ++k)
+    if (m == (1 << k)) p.log2_grid_m = k;
+  p.width = o->width;
+  p.height = o->height;
+  p.aa_kind = o->aa_kind;
+  p.grid_m = m;
+  p.spp = spp;
+}
+
 int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, FastParams& p, int* blocks,
               rt_scene::Order** measuring, hipStream_t st, bool* split, unsigned int* zero, int nzero, bool* zeroed) {
   std::memset(&p, 0, sizeof p);
@@ -1716,38 +1753,13 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   p.fb = fb;
   p.partials = s->partials.p;
   p.queue = s->queue.p;
-  // camera: origin = C2W * (0,0,0,1) = column 3; dir = C2W * normalize(cx, cy, -1, 0)
-  for (int k = 0; k < 3; ++k) {
-    p.cam[k] = (float)s->c2w[12 + k];
-    p.cam[3 + k] = (float)s->c2w[0 + k];
-    p.cam[6 + k] = (float)s->c2w[4 + k];
-    p.cam[9 + k] = (float)s->c2w[8 + k];
-  }
-  const double f = std::tan(s->fov * (3.14159265358979323846 / 180.0) / 2);
-  const double r = (double)o->width / (double)o->height;
-  p.cam_a = (float)(2.0 * r * f / (double)o->width);  // cx = ((2 x r)/w - r) f = (x - w/2) 2rf/w
-  p.cam_b = (float)(0.5 * (double)o->width);
-  p.cam_c = (float)(2.0 * f / (double)o->height);     // cy = (1 - 2y/h) f = (h/2 - y) 2f/h
-  p.cam_d = (float)(0.5 * (double)o->height);
+  fast_camera(s->c2w, s->fov, o, p);
+  const int spp = p.spp;
   for (int k = 0; k < 3; ++k) p.bg[k] = (float)s->bg[k];
-  p.bias = (float)o->bias;
-  const int m = o->aa_kind != RT_AA_NONE ? o->grid_size : 1;
-  const int spp = m * m;
-  p.inv_len = (float)(1.0 / (double)spp);
-  p.sample_step = (float)(1.0 / (double)m);
-  p.sample_off = (float)(1.0 / (double)m * 0.5);
-  p.log2_grid_m = -1;
-  for (int k = 0; k <= 12; ++k)
-    if (m == (1 << k)) p.log2_grid_m = k;
   p.nobj = s->nobj;
   p.nlight = s->nlight;
   p.has_point_light = s->has_point_light;
   p.seed = o->seed;
-  p.width = o->width;
-  p.height = o->height;
-  p.aa_kind = o->aa_kind;
-  p.grid_m = m;
-  p.spp = spp;
   p.max_depth = o->max_ray_depth;
   p.flags = (int32_t)o->flags;
   p.shadow_mesh = s->shadow_mesh;
@@ -2679,6 +2691,83 @@ extern "C" int rtmi_test_pixel_info(rt_scene* s, uint32_t* info) {
   if (!f.info.p || f.w == 0) return fail(RT_E_INVALID, "no per-call records yet");
   HIP_TRY(hipEventSynchronize(s->done));
   HIP_TRY(hipMemcpy(info, f.info.p, (size_t)f.w * (size_t)f.h * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// Test hooks for the uniform-pixel proof (tests/test_uniform_cpu.py; no
+// device): the FastParams camera words and the UniformCam of a one-plane call
+// with this camera, image size, m x m grid and bias, formed by the functions
+// a render call forms them with (fast_camera, uniform_cam). ty: the plane's
+// world_to_object[13] and light_dirs: nl x 3 doubles, both rounded as
+// fill_fast_records rounds them. cls: uniform_class of the pixels
+// [x0, x1) x [y0, y1), row by row; cam10: cam_a, cam_b, cam_c, cam_d, c4,
+// c7, c10, st, of, nroy.
+static int uniform_hook_cam(const double* c2w, double fov, int32_t w, int32_t h, int32_t m, double ty, double bias,
+                            const double* light_dirs, int32_t nl, bg::UniformCam& u) {
+  if (!c2w || w <= 0 || h <= 0 || m <= 0 || nl < 0 || nl > 8 || (nl > 0 && !light_dirs))
+    return fail(RT_E_INVALID, "bad argument");
+  rt_options o;
+  std::memset(&o, 0, sizeof o);
+  o.width = w;
+  o.height = h;
+  o.aa_kind = RT_AA_GRID;
+  o.grid_size = m;
+  o.bias = bias;
+  FastParams p;
+  std::memset(&p, 0, sizeof p);
+  fast_camera(c2w, fov, &o, p);
+  p.nlight = nl;
+  float vy[8];
+  for (int l = 0; l < nl; ++l) vy[l] = (float)light_dirs[3 * l + 1];
+  std::memset(&u, 0, sizeof u);
+  uniform_cam((float)ty, vy, p, u);
+  return RT_OK;
+}
+
+extern "C" int rtmi_test_uniform(const double* c2w, double fov, int32_t w, int32_t h, int32_t m, double ty,
+                                 double bias, const double* light_dirs, int32_t nl, int32_t x0, int32_t y0, int32_t x1,
+                                 int32_t y1, uint8_t* cls, int32_t* lit_ok, float* cam10) {
+  bg::UniformCam u;
+  if (int rc = uniform_hook_cam(c2w, fov, w, h, m, ty, bias, light_dirs, nl, u)) return rc;
+  if (!cls || !lit_ok || !cam10 || x0 < 0 || y0 < 0 || x1 > w || y1 > h || x0 > x1 || y0 > y1)
+    return fail(RT_E_INVALID, "bad argument");
+  for (int y = y0; y < y1; ++y)
+    for (int x = x0; x < x1; ++x) *cls++ = (uint8_t)bg::uniform_class(u, x, y);
+  *lit_ok = u.lit_ok;
+  const float c[10] = {u.cam_a, u.cam_b, u.cam_c, u.cam_d, u.c4, u.c7, u.c10, u.st, u.of, u.nroy};
+  std::copy(c, c + 10, cam10);
+  return RT_OK;
+}
+
+// The one-plane kernel's cx (m per pixel column), cy (m per pixel row) and N
+// (m x m per pixel: pixels row by row, then the sample row j, then the sample
+// column i) for every sample of the same rectangle: the expressions listed
+// above rt_bins_geom.h uniform_class, with fmaf where the kernel has an fma
+// (this file is compiled without contraction).
+extern "C" int rtmi_test_uniform_samples(const double* c2w, double fov, int32_t w, int32_t h, int32_t m, double ty,
+                                         double bias, int32_t x0, int32_t y0, int32_t x1, int32_t y1, float* cx,
+                                         float* cy, float* n) {
+  bg::UniformCam u;
+  if (int rc = uniform_hook_cam(c2w, fov, w, h, m, ty, bias, nullptr, 0, u)) return rc;
+  if (!cx || !cy || !n || x0 < 0 || y0 < 0 || x1 > w || y1 > h || x0 > x1 || y0 > y1)
+    return fail(RT_E_INVALID, "bad argument");
+  for (int x = x0; x < x1; ++x)
+    for (int i = 0; i < m; ++i) {
+      const float px = (float)x + fmaf((float)i, u.st, u.of);
+      cx[(size_t)(x - x0) * m + i] = (px - u.cam_b) * u.cam_a;
+    }
+  for (int y = y0; y < y1; ++y)
+    for (int j = 0; j < m; ++j) {
+      const float py = (float)y + fmaf((float)j, u.st, u.of);
+      cy[(size_t)(y - y0) * m + j] = (u.cam_d - py) * u.cam_c;
+    }
+  for (int y = y0; y < y1; ++y)
+    for (int x = x0; x < x1; ++x)
+      for (int j = 0; j < m; ++j) {
+        const float cyj = cy[(size_t)(y - y0) * m + j];
+        for (int i = 0; i < m; ++i)
+          *n++ = fmaf(cyj, u.c7, fmaf(cx[(size_t)(x - x0) * m + i], u.c4, -u.c10));
+      }
   return RT_OK;
 }
 
