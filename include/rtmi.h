@@ -525,6 +525,88 @@ int rt_scene_last_uniform(rt_scene *scene, int32_t *lit, int32_t *sky);
  * the call. */
 int rt_scene_last_ground(rt_scene *scene, int32_t *ground);
 
+/* ---- ray queries --------------------------------------------------------
+ * trace (renderer.nim:47-67) itself — "what does this ray hit, and where" —
+ * for batches of caller-supplied rays and for picks through the camera:
+ * what a GUI needs for the object under the mouse, a tool to place something
+ * on a surface, a line-of-sight test. float64 only: the answers are the
+ * reference's, operation for operation (there is no float32 mode).
+ *
+ * Ray i is the world-space (orig[3i..3i+2], 1), (dir[3i..3i+2], 0) of initRay
+ * (geom.nim:41-48); dir is taken as given, NOT normalised, so t is in units
+ * of |dir|. The answer is trace(ray, scene.objects, tNear): the closest t
+ * with 0 <= t < t_near, the first object in scene order on equal t, the
+ * lowest face index on equal t within a mesh — including
+ * TriangleMesh.intersect's AABB gate (geom.nim:339-358): a ray that starts
+ * inside a mesh's box misses that mesh. t_near == NULL means +inf for every
+ * ray.
+ *  - Miss: obj = -1, face = -1, t = that ray's t_near.
+ *  - RT_QUERY_ANY_HIT: trace as shade calls it for shadow rays (renderer.nim:
+ *    96-99), with their exact early exit: only obj >= 0 versus obj == -1 is
+ *    meaningful. t and face are not computed (t echoes t_near, face is -1).
+ *    The Stats are still the reference's.
+ *  - A degenerate ray — a non-finite component, an all-zero direction or a
+ *    NaN t_near — is answered as a miss with its t_near as given and adds
+ *    nothing to the Stats.
+ *  - normals (may be NULL) receives per ray the vector shade calls hitNormal
+ *    (renderer.nim:83-88): objectToWorld * normal(hitO) for spheres, planes
+ *    and boxes, objectToWorld * normals[face] for mesh hits; xyz, not
+ *    renormalised; (0, 0, 0) on a miss. RT_E_INVALID with RT_QUERY_ANY_HIT.
+ *  - out (may be NULL) receives num_intersection_tests and
+ *    num_intersection_hits as renderer.nim:58,65 count them over the batch,
+ *    the other fields 0 (picks: num_primary_rays, see rt_pick_pixels).
+ *    A _device call with out == NULL only enqueues work on hip_stream; with
+ *    out it waits for the answers.
+ *  - RT_QUERY_SORT: the rays are traced in the order of a 32-bit coherence
+ *    key formed on the device (direction octant, then a Morton code of the
+ *    origin within the batch's origin bounds, or of the direction when every
+ *    ray shares one origin; picks: a Morton code of the pixel position), the
+ *    answers written back in input order: hits, normals and Stats are the
+ *    same, byte for byte. Whether it is faster depends on the batch
+ *    (DESIGN.md "Ray queries"); off by default.
+ * Queries take the scene's lock, are ordered after a render still in flight
+ * on the scene, and leave what rt_scene_last_stats, _last_split, _last_batch,
+ * _last_lean_kernel, _last_uniform, _last_ground, _last_timing and
+ * _last_counters report untouched: those stay the last render call's.
+ * n == 0 is RT_OK and launches nothing; n < 0, unknown flag bits and null
+ * required pointers are RT_E_INVALID; n >= 2^31 is RT_E_UNSUPPORTED. */
+typedef struct rt_hit {     /* 16 bytes */
+  double  t;                /* tHit; on a miss: that ray's t_near          */
+  int32_t obj;              /* index into rt_scene_desc.objects, -1 = nil  */
+  int32_t face;             /* original face index of a mesh hit, else -1  */
+} rt_hit;
+
+#define RT_QUERY_ANY_HIT 0x1u  /* shadow-ray semantics */
+#define RT_QUERY_SORT    0x2u  /* reorder rays for coherence before tracing */
+
+/* Device form: d_orig / d_dir (n*3 doubles), d_tnear (n doubles or NULL),
+ * d_hits (n rt_hit) and d_normals (n*3 doubles or NULL) are device memory. */
+int rt_trace_rays_device(rt_scene *scene, int64_t n, const double *d_orig,
+                         const double *d_dir, const double *d_tnear,
+                         uint32_t flags, rt_hit *d_hits, double *d_normals,
+                         void *hip_stream, rt_stats *out);
+/* Host form: the same arrays in caller memory; returns with the answers. */
+int rt_trace_rays(rt_scene *scene, int64_t n, const double *orig,
+                  const double *dir, const double *tnear, uint32_t flags,
+                  rt_hit *hits, double *normals, rt_stats *out);
+
+/* Picking: ray i is castPrimaryRay(opts->width, opts->height, xy[2i],
+ * xy[2i+1], fov, cameraToWorld) (renderer.nim:31-44) with the scene's current
+ * camera (rt_scene_set_camera applies), formed on the device exactly as the
+ * float64 render forms it, and traced with t_near = +inf. Integer (x, y) is
+ * the akNone sample of that pixel; fractional coordinates and coordinates
+ * outside the image are legal; a non-finite coordinate makes the ray
+ * degenerate. Only width, height and precision of opts are read; precision
+ * must be RT_FP64 (RT_E_UNSUPPORTED otherwise). flags, hits, normals and out
+ * as above; out->num_primary_rays is the number of rays that are not
+ * degenerate. */
+int rt_pick_pixels_device(rt_scene *scene, const rt_options *opts, int64_t n,
+                          const double *d_xy, uint32_t flags, rt_hit *d_hits,
+                          double *d_normals, void *hip_stream, rt_stats *out);
+int rt_pick_pixels(rt_scene *scene, const rt_options *opts, int64_t n,
+                   const double *xy, uint32_t flags, rt_hit *hits,
+                   double *normals, rt_stats *out);
+
 /* ---- helpers ----------------------------------------------------------- */
 
 /* glm-style inverse of a column-major 4x4 (what geom.nim's

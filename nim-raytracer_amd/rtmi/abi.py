@@ -35,6 +35,8 @@ RT_FLAG_COMPACT = 0x2000
 RT_FLAG_F64_PER_LANE = 0x4000
 RT_FLAG_NO_UNIFORM = 0x8000
 RT_FLAG_NO_GROUND1 = 0x10000
+RT_QUERY_ANY_HIT = 0x1
+RT_QUERY_SORT = 0x2
 RT_BVH_SAH = 0
 RT_OBJ_SLASH_INDICES = 0x1
 RT_BVH_PLOC = 1
@@ -130,6 +132,14 @@ class rt_response(C.Structure):
     ]
 
 
+class rt_hit(C.Structure):
+    _fields_ = [
+        ("t", C.c_double),
+        ("obj", C.c_int32),
+        ("face", C.c_int32),
+    ]
+
+
 RT_QUEUE_STOPPED, RT_QUEUE_RUNNING, RT_QUEUE_SHUTDOWN = 0, 1, 2
 
 
@@ -219,6 +229,14 @@ SIGNATURES = {
     "rt_queue_reset": (C.c_int, [_P]),
     "rt_queue_shutdown": (C.c_int, [_P]),
     "rt_queue_destroy": (C.c_int, [_P]),
+    "rt_trace_rays_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(rt_stats)]),
+    "rt_trace_rays": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), C.c_uint32, C.POINTER(rt_hit), C.POINTER(C.c_double),
+                                C.POINTER(rt_stats)]),
+    "rt_pick_pixels_device": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, _P, C.c_uint32, _P, _P, _P,
+                                        C.POINTER(rt_stats)]),
+    "rt_pick_pixels": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_double), C.c_uint32,
+                                 C.POINTER(rt_hit), C.POINTER(C.c_double), C.POINTER(rt_stats)]),
 }
 
 

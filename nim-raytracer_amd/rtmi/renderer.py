@@ -107,6 +107,74 @@ class DeviceScene:
                                            int(world), _stream(stream), C.byref(st) if stats else None))
         return Stats.from_c(st) if stats else None
 
+    # -- ray queries (rt_trace_rays* / rt_pick_pixels*) ----------------------
+    def trace_rays(self, orig, dir, t_near=None, any_hit=False, sort=False, normals=False, stats=False,
+                   stream=None):
+        """trace (renderer.nim:47-67) for n rays: orig and dir are (n, 3)
+        float64 — numpy arrays (the host form) or CUDA torch tensors (the
+        device form, enqueued on `stream`; it waits only with stats=True) —
+        dir as given, not normalised; t_near (n,) or None for +inf. Returns
+        (t, obj, face[, normals][, Stats]) as arrays of the same kind: t is
+        the ray's t_near and obj / face are -1 on a miss; with any_hit only
+        obj >= 0 / obj == -1 is meaningful; sort traces the rays in a
+        coherence order (the same answers); normals: shade's hitNormal per
+        hit, (0, 0, 0) on a miss. The device form's t / obj / face are views
+        of one (n, 2) float64 tensor."""
+        flags = (abi.RT_QUERY_ANY_HIT if any_hit else 0) | (abi.RT_QUERY_SORT if sort else 0)
+        if _is_host(orig):
+            o, d = _host_f64(orig, (-1, 3)), _host_f64(dir, (-1, 3))
+            n = o.shape[0]
+            if d.shape[0] != n:
+                raise ValueError("orig and dir must hold the same number of rays")
+            tn = None if t_near is None else _host_f64(t_near, (n,))
+            return self._query_host(n, flags, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays(
+                self.h, n, _dptr(o), _dptr(d), _dptr(tn), flags, hits, nrm, st))
+        n = _dev_f64(orig, None, 3)
+        _dev_f64(dir, n, 3)
+        if t_near is not None:
+            _dev_f64(t_near, n, 1)
+        return self._query_device(orig, n, flags, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_device(
+            self.h, n, C.c_void_p(orig.data_ptr()), C.c_void_p(dir.data_ptr()),
+            C.c_void_p(t_near.data_ptr()) if t_near is not None else None, flags, hits, nrm, _stream(stream), st))
+
+    def pick(self, opts: Options, xy, any_hit=False, sort=False, normals=False, stats=False, stream=None):
+        """What is under image position xy[i] = (x, y): castPrimaryRay
+        (renderer.nim:31-44) through the scene's current camera for an
+        opts.width x opts.height image (opts.precision must be fp64), then
+        trace with t_near = +inf. Integer (x, y) is the akNone sample of that
+        pixel; fractional and out-of-image positions are legal. xy is (n, 2)
+        float64, numpy or CUDA torch; returns as trace_rays does, the Stats'
+        numPrimaryRays counting the rays that are not degenerate."""
+        flags = (abi.RT_QUERY_ANY_HIT if any_hit else 0) | (abi.RT_QUERY_SORT if sort else 0)
+        o = opts.to_c()
+        if _is_host(xy):
+            p = _host_f64(xy, (-1, 2))
+            n = p.shape[0]
+            return self._query_host(n, flags, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels(
+                self.h, C.byref(o), n, _dptr(p), flags, hits, nrm, st))
+        n = _dev_f64(xy, None, 2)
+        return self._query_device(xy, n, flags, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_device(
+            self.h, C.byref(o), n, C.c_void_p(xy.data_ptr()), flags, hits, nrm, _stream(stream), st))
+
+    def _query_host(self, n, flags, normals, stats, call):
+        hits = np.zeros(n, dtype=_HIT_DTYPE)
+        nrm = np.zeros((n, 3), dtype=np.float64) if normals else None
+        st = abi.rt_stats()
+        check(call(hits.ctypes.data_as(C.POINTER(abi.rt_hit)), _dptr(nrm), C.byref(st) if stats else None))
+        out = (hits["t"].copy(), hits["obj"].copy(), hits["face"].copy())
+        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
+
+    def _query_device(self, like, n, flags, normals, stats, call):
+        import torch
+        hits = torch.empty((n, 2), dtype=torch.float64, device=like.device)
+        nrm = torch.empty((n, 3), dtype=torch.float64, device=like.device) if normals else None
+        st = abi.rt_stats()
+        check(call(C.c_void_p(hits.data_ptr()), C.c_void_p(nrm.data_ptr()) if normals else None,
+                   C.byref(st) if stats else None))
+        words = hits.view(torch.int32)
+        out = (hits[:, 0], words[:, 2], words[:, 3])
+        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
+
     def last_pipelined(self):
         """Whether the last render call was pipelined (its build on the
         scene's build stream, its own buffer set: rtmi.cpp rt_scene::pipe) —
@@ -577,6 +645,34 @@ def _ptr(buf, min_floats):
         return int(buf.data_ptr())
     except AttributeError:
         raise TypeError("device buffer must be an int pointer or a torch tensor") from None
+
+
+# rt_hit (include/rtmi.h) as a numpy record
+_HIT_DTYPE = np.dtype([("t", np.float64), ("obj", np.int32), ("face", np.int32)])
+
+
+def _is_host(a):
+    """numpy (or a plain sequence): the host form; a CUDA torch tensor: the device form."""
+    return not hasattr(a, "data_ptr")
+
+
+def _host_f64(a, shape):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+
+
+def _dptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _dev_f64(t, n, width):
+    """Check a device array of n (or any number of) rows of `width` float64; returns the row count."""
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise ValueError("device arrays must be contiguous float64 CUDA/HIP tensors")
+    if t.numel() % width or (n is not None and t.numel() != n * width):
+        raise ValueError(f"device array holds {t.numel()} doubles, expected "
+                         f"{'a multiple of ' + str(width) if n is None else n * width}")
+    return t.numel() // width
 
 
 def _stream(stream):
