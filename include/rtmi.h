@@ -315,6 +315,20 @@ int rt_scene_get_info(const rt_scene *scene, rt_scene_info *out);
 int rt_scene_set_camera(rt_scene *scene, const double camera_to_world[16],
                         double fov_deg);
 
+/* Replace the scene's lights (Scene.lights, scene.nim). From the next call on
+ * the scene behaves exactly as one created by rt_scene_create from the same
+ * description with these lights: frames in both precisions, Stats, the
+ * rt_scene_last_* diagnostics and which kernels run are the same, bit for bit.
+ * Any count >= 0 and any mix of light types; the count and types may differ
+ * from the current ones. Geometry, BVH, triangle records, camera and buffer
+ * sets are kept; the distant lights' mesh grids are rebuilt on the device from
+ * the resident faces. Waits for the scene's earlier calls (renders, pipelined
+ * builds, queries). RT_E_INVALID for a negative count, a null array with a
+ * non-zero count or a bad light type. On any failure the scene keeps its
+ * previous lights. */
+int rt_scene_set_lights(rt_scene *scene, const rt_light_desc *lights,
+                        int32_t num_lights);
+
 /* ---- rendering ----------------------------------------------------------
  * All render calls implement renderLine (renderer.nim:162-211) for every row
  * y in countup(y0, y1 - 1, step):
@@ -398,6 +412,9 @@ int rt_render_frame_multi(rt_multi *m, const rt_options *opts, float *fb,
 /* rt_scene_set_camera on every rank's scene. */
 int rt_multi_set_camera(rt_multi *m, const double camera_to_world[16],
                         double fov_deg);
+/* rt_scene_set_lights on every rank's scene. */
+int rt_multi_set_lights(rt_multi *m, const rt_light_desc *lights,
+                        int32_t num_lights);
 int rt_multi_destroy(rt_multi *m);
 
 /* ---- render queue (workerpool.nim WorkerPool[WorkMsg, ResponseMsg]) ---- */

@@ -69,79 +69,6 @@ bool invert4(const double m[16], double inv[16]) {
   return true;
 }
 
-// The single-sided test rejects det < 1e-6 (geom.nim:306). det is computed
-// in float32 from the object-space direction rd and nn = -(e1 x e2); a face
-// is left out of a family's bins only when det stays below 1e-6 even with a
-// float32 error of 1e-6 * |rd| * |nn| (generous: the test's own rounding is
-// ~1e-7 of that).
-inline bool never_passes(double det_upper, double rd_max, double nlen) {
-  return det_upper + 1e-6 * rd_max * nlen < 1e-6;
-}
-
-// Separating-axis test of a 2D triangle against the box [x0, x1] x [y0, y1]
-// (the box axes are the caller's bounding-rectangle loop): false only when
-// one triangle edge has all four box corners strictly outside it.
-// Area of the 2D triangle q[0..5] (x, y pairs) inside the box [x0, x1] x
-// [y0, y1]: Sutherland-Hodgman against the four edges, then the shoelace.
-inline double clipped_area(const double* q, double x0, double y0, double x1, double y1) {
-  double a[16][2], b[16][2];
-  int n = 3;
-  for (int k = 0; k < 3; ++k) {
-    a[k][0] = q[2 * k];
-    a[k][1] = q[2 * k + 1];
-  }
-  // edge e: keep points with s * p[axis] <= s * lim
-  const int axis[4] = {0, 0, 1, 1};
-  const double lim[4] = {x0, x1, y0, y1}, sgn[4] = {-1.0, 1.0, -1.0, 1.0};
-  for (int ei = 0; ei < 4 && n > 0; ++ei) {
-    const int ax = axis[ei];
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-      const double* P = a[k];
-      const double* Q = a[(k + 1) % n];
-      const double dp = sgn[ei] * (P[ax] - lim[ei]), dq = sgn[ei] * (Q[ax] - lim[ei]);
-      if (dp <= 0.0) {
-        b[m][0] = P[0];
-        b[m][1] = P[1];
-        ++m;
-      }
-      if ((dp < 0.0 && dq > 0.0) || (dp > 0.0 && dq < 0.0)) {
-        const double t = dp / (dp - dq);
-        b[m][0] = P[0] + t * (Q[0] - P[0]);
-        b[m][1] = P[1] + t * (Q[1] - P[1]);
-        ++m;
-      }
-    }
-    n = m;
-    for (int k = 0; k < n; ++k) {
-      a[k][0] = b[k][0];
-      a[k][1] = b[k][1];
-    }
-  }
-  double area = 0.0;
-  for (int k = 0; k < n; ++k) {
-    const double* P = a[k];
-    const double* Q = a[(k + 1) % n];
-    area += P[0] * Q[1] - Q[0] * P[1];
-  }
-  return 0.5 * std::fabs(area);
-}
-
-inline bool tri_meets_box(const double* q, double x0, double y0, double x1, double y1) {
-  const double area = (q[2] - q[0]) * (q[5] - q[1]) - (q[3] - q[1]) * (q[4] - q[0]);
-  if (!(area != 0.0)) return true;  // degenerate (or NaN): keep
-  const double sg = area > 0.0 ? 1.0 : -1.0;
-  const double cx[4] = {x0, x1, x0, x1}, cy[4] = {y0, y0, y1, y1};
-  for (int k = 0; k < 3; ++k) {
-    const double ax = q[2 * k], ay = q[2 * k + 1];
-    const double bx = q[2 * ((k + 1) % 3)], by = q[2 * ((k + 1) % 3) + 1];
-    double best = -INFINITY;
-    for (int c = 0; c < 4; ++c) best = std::max(best, sg * ((bx - ax) * (cy[c] - ay) - (by - ay) * (cx[c] - ax)));
-    if (best < 0.0) return false;
-  }
-  return true;
-}
-
 // Two-pass bucket fill: count[k] entries per bin -> off (prefix) -> ent.
 template <class Emit>
 bool fill_bins(size_t nbins, size_t ntri, Emit emit, std::vector<int32_t>& off, std::vector<int32_t>& ent,
@@ -250,82 +177,7 @@ bool build_pixel_bins(const std::vector<BinTri>& tris, const double o2w[16], con
   return fill_bins((size_t)width * (size_t)height, tris.size(), emit, out->off, out->ent, why);
 }
 
-bool build_light_grid(const std::vector<BinTri>& tris, const double w2o[16], const double dir[3],
-                      LightGridHost* out, const char** why) {
-  *why = "";
-  out->g = LightGrid{};
-  const double sd[3] = {-dir[0], -dir[1], -dir[2]};
-  double rd[3];
-  xform_dir(w2o, sd, rd);  // object-space shadow direction (the kernel's rd, up to float32 rounding)
-  const double rlen = norm3(rd);
-  if (!(rlen > 0.0) || !std::isfinite(rlen)) {
-    *why = "degenerate light direction";
-    return false;
-  }
-  const double u[3] = {rd[0] / rlen, rd[1] / rlen, rd[2] / rlen};
-  // basis orthogonal to the shadow direction
-  const int ax = std::fabs(u[0]) <= std::fabs(u[1]) && std::fabs(u[0]) <= std::fabs(u[2]) ? 0
-                 : std::fabs(u[1]) <= std::fabs(u[2])                                 ? 1
-                                                                                      : 2;
-  double a[3] = {0, 0, 0};
-  a[ax] = 1.0;
-  double e1[3], e2[3];
-  cross3(a, u, e1);
-  const double l1 = norm3(e1);
-  for (double& x : e1) x /= l1;
-  cross3(u, e1, e2);
-  double scale = 1.0;
-  for (const BinTri& t : tris)
-    for (int v = 0; v < 3; ++v)
-      for (int k = 0; k < 3; ++k) scale = std::max(scale, std::fabs(t.v[v][k]));
-  const double delta = 1e-5 * scale;
-  std::vector<double> box(tris.size() * 4, NAN), proj(tris.size() * 6, 0.0);
-  double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
-  size_t kept = 0;
-  for (size_t i = 0; i < tris.size(); ++i) {
-    const BinTri& t = tris[i];
-    double f1[3], f2[3], c[3], nn[3];
-    for (int k = 0; k < 3; ++k) {
-      f1[k] = t.v[1][k] - t.v[0][k];
-      f2[k] = t.v[2][k] - t.v[0][k];
-    }
-    cross3(f1, f2, c);
-    for (int k = 0; k < 3; ++k) nn[k] = -c[k];
-    if (never_passes(dot3(rd, nn), rlen, norm3(nn))) continue;  // faces away from the light
-    double bu0 = INFINITY, bu1 = -INFINITY, bv0 = INFINITY, bv1 = -INFINITY;
-    for (int v = 0; v < 3; ++v) {
-      const double pu = dot3(t.v[v], e1), pv = dot3(t.v[v], e2);
-      proj[6 * i + 2 * v] = pu;
-      proj[6 * i + 2 * v + 1] = pv;
-      bu0 = std::min(bu0, pu);
-      bu1 = std::max(bu1, pu);
-      bv0 = std::min(bv0, pv);
-      bv1 = std::max(bv1, pv);
-    }
-    box[4 * i + 0] = bu0 - delta;
-    box[4 * i + 1] = bu1 + delta;
-    box[4 * i + 2] = bv0 - delta;
-    box[4 * i + 3] = bv1 + delta;
-    umin = std::min(umin, box[4 * i + 0]);
-    umax = std::max(umax, box[4 * i + 1]);
-    vmin = std::min(vmin, box[4 * i + 2]);
-    vmax = std::max(vmax, box[4 * i + 3]);
-    ++kept;
-  }
-  LightGrid& g = out->g;
-  for (int k = 0; k < 3; ++k) {
-    g.e1[k] = (float)e1[k];
-    g.e2[k] = (float)e2[k];
-  }
-  g.rmax = (float)(100.0 * scale);
-  if (kept == 0) {  // nothing faces the light: every lane misses (an empty 1x1 grid)
-    g.u0 = g.v0 = 0.0f;
-    g.inv_h = 1.0f;
-    g.gu = g.gv = 1;
-    out->off.assign(2, 0);
-    out->ent.assign(kBinPad, tris.empty() ? 0 : tris[0].rec);
-    return true;
-  }
+double light_grid_density() {
   // about 2 cells per listed face (RTMI_GRID_DENSITY), square cells, at most
   // 4096 per side. Coarse cells measured best on C3: density 1 / 2 / 4 / 8 /
   // 16 / 32 -> 4.91 / 4.89 / 4.92 / 4.96 / 5.09 / 5.76 ms (fewer distinct
@@ -335,32 +187,53 @@ bool build_light_grid(const std::vector<BinTri>& tris, const double w2o[16], con
     const double v = e ? std::atof(e) : 2.0;
     return v > 0.0 ? v : 2.0;
   }();
-  const double du = std::max(umax - umin, 1e-30), dv = std::max(vmax - vmin, 1e-30);
-  double h = std::sqrt(du * dv / (density * (double)kept));
-  h = std::max(h, std::max(du, dv) / 4096.0);
-  const int gu = std::max(1, std::min(4096, (int)std::ceil(du / h)));
-  const int gv = std::max(1, std::min(4096, (int)std::ceil(dv / h)));
-  // the float32 origin / cell size the kernel uses, so host and device agree on
-  // cell edges up to float32 rounding (covered by delta)
-  g.u0 = (float)umin;
-  g.v0 = (float)vmin;
-  g.inv_h = (float)(1.0 / h);
-  g.gu = gu;
-  g.gv = gv;
-  const double ih = (double)g.inv_h;
+  return density;
+}
+
+// The geometry is rt_bins_geom.h's (light_basis .. light_cell_cover), shared
+// with the device builder (rt_lights_gpu.hip), which must form the same arrays.
+bool build_light_grid(const std::vector<BinTri>& tris, const double w2o[16], const double dir[3],
+                      LightGridHost* out, const char** why) {
+  *why = "";
+  out->g = LightGrid{};
+  bg::LightBasis lb;
+  if (!bg::light_basis(w2o, dir, &lb)) {
+    *why = "degenerate light direction";
+    return false;
+  }
+  double scale = 1.0;
+  for (const BinTri& t : tris) scale = bg::light_face_scale(scale, t.v);
+  const double delta = 1e-5 * scale;
+  std::vector<double> box(tris.size() * 4, NAN), proj(tris.size() * 6, 0.0);
+  double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
+  size_t kept = 0;
+  for (size_t i = 0; i < tris.size(); ++i) {
+    double q[6], bx[4];
+    if (!bg::light_face_box(lb, tris[i].v, delta, q, bx)) continue;  // faces away from the light
+    for (int k = 0; k < 6; ++k) proj[6 * i + k] = q[k];
+    for (int k = 0; k < 4; ++k) box[4 * i + k] = bx[k];
+    umin = std::min(umin, box[4 * i + 0]);
+    umax = std::max(umax, box[4 * i + 1]);
+    vmin = std::min(vmin, box[4 * i + 2]);
+    vmax = std::max(vmax, box[4 * i + 3]);
+    ++kept;
+  }
+  LightGrid& g = out->g;
+  bg::light_grid_header(lb, scale, (long long)kept, umin, umax, vmin, vmax, light_grid_density(), &g);
+  if (kept == 0) {  // nothing faces the light: every lane misses (an empty 1x1 grid)
+    out->off.assign(2, 0);
+    out->ent.assign(kBinPad, tris.empty() ? 0 : tris[0].rec);
+    return true;
+  }
+  const int gu = g.gu, gv = g.gv;
   auto emit = [&](size_t i, auto&& put) {
     if (std::isnan(box[4 * i])) return;
-    const int c0 = std::max(0, (int)std::floor((box[4 * i + 0] - (double)g.u0) * ih));
-    const int c1 = std::min(gu - 1, (int)std::floor((box[4 * i + 1] - (double)g.u0) * ih));
-    const int r0 = std::max(0, (int)std::floor((box[4 * i + 2] - (double)g.v0) * ih));
-    const int r1 = std::min(gv - 1, (int)std::floor((box[4 * i + 3] - (double)g.v0) * ih));
+    int rc[4];
+    bg::light_cell_range(g, &box[4 * i], rc);
     const double* q = &proj[6 * i];
-    for (int r = r0; r <= r1; ++r)
-      for (int c = c0; c <= c1; ++c) {
-        const double cu0 = (double)g.u0 + c / ih, cv0 = (double)g.v0 + r / ih;
-        if (tri_meets_box(q, cu0 - delta, cv0 - delta, cu0 + 1.0 / ih + delta, cv0 + 1.0 / ih + delta))
-          put((size_t)r * (size_t)gu + (size_t)c, tris[i].rec);
-      }
+    for (int r = rc[2]; r <= rc[3]; ++r)
+      for (int c = rc[0]; c <= rc[1]; ++c)
+        if (bg::light_face_in_cell(g, q, delta, c, r)) put((size_t)r * (size_t)gu + (size_t)c, tris[i].rec);
   };
   if (!fill_bins((size_t)gu * (size_t)gv, tris.size(), emit, out->off, out->ent, why)) return false;
   out->box = box;
@@ -374,19 +247,17 @@ bool build_light_grid(const std::vector<BinTri>& tris, const double w2o[16], con
   face_of.reserve(tris.size());
   for (size_t i = 0; i < tris.size(); ++i)
     if (!std::isnan(box[4 * i])) face_of.emplace(tris[i].rec, (int32_t)i);
-  const double hc = 1.0 / ih;
   std::vector<std::pair<double, int32_t>> row;
   for (int r = 0; r < gv; ++r)
     for (int c = 0; c < gu; ++c) {
       const size_t cell = (size_t)r * (size_t)gu + (size_t)c;
       const int32_t b = out->off[cell], e = out->off[cell + 1];
       if (e - b < 2) continue;
-      const double cu0 = (double)g.u0 + c * hc, cv0 = (double)g.v0 + r * hc;
       row.clear();
       for (int32_t k = b; k < e; ++k) {
         const int32_t rec = out->ent[(size_t)k];
         const auto it = face_of.find(rec);
-        const double cov = it == face_of.end() ? 0.0 : clipped_area(&proj[6 * (size_t)it->second], cu0, cv0, cu0 + hc, cv0 + hc);
+        const double cov = it == face_of.end() ? 0.0 : bg::light_cell_cover(g, &proj[6 * (size_t)it->second], c, r);
         row.emplace_back(-cov, rec);
       }
       std::stable_sort(row.begin(), row.end(),

@@ -69,6 +69,8 @@ struct LightGridHost {
 // dir: the light's travel direction (world); shadow rays go along -dir.
 bool build_light_grid(const std::vector<BinTri>& tris, const double w2o[16], const double dir[3],
                       LightGridHost* out, const char** why);
+// Cells per listed face of a light grid (RTMI_GRID_DENSITY, default 2).
+double light_grid_density();
 
 // Shadow skips. Per pixel, bit l (l < 8): every shadow ray to distant light
 // l that leaves a camera hit of this pixel provably meets no face of the mesh,

@@ -58,6 +58,215 @@ __host__ __device__ inline bool tri_meets_box(const double* q, double x0, double
   return true;
 }
 
+// ---- light grids (rt_bins.cpp build_light_grid, rt_lights_gpu.hip) ---------
+//
+// The host builder and the device builder of a distant light's grid call the
+// same functions below, so every bound, cell range and coverage is the same
+// float64 value on both sides and the two build the same arrays.
+
+// Area of the 2D triangle q[0..5] (x, y pairs) inside the box [x0, x1] x
+// [y0, y1]: Sutherland-Hodgman against the four edges, then the shoelace.
+__host__ __device__ inline double clipped_area(const double* q, double x0, double y0, double x1, double y1) {
+  double a[16][2], b[16][2];
+  int n = 3;
+  for (int k = 0; k < 3; ++k) {
+    a[k][0] = q[2 * k];
+    a[k][1] = q[2 * k + 1];
+  }
+  // edge e: keep points with s * p[axis] <= s * lim
+  const int axis[4] = {0, 0, 1, 1};
+  const double lim[4] = {x0, x1, y0, y1}, sgn[4] = {-1.0, 1.0, -1.0, 1.0};
+  for (int ei = 0; ei < 4 && n > 0; ++ei) {
+    const int ax = axis[ei];
+    int m = 0;
+    for (int k = 0; k < n; ++k) {
+      const double* P = a[k];
+      const double* Q = a[(k + 1) % n];
+      const double dp = sgn[ei] * (P[ax] - lim[ei]), dq = sgn[ei] * (Q[ax] - lim[ei]);
+      if (dp <= 0.0) {
+        b[m][0] = P[0];
+        b[m][1] = P[1];
+        ++m;
+      }
+      if ((dp < 0.0 && dq > 0.0) || (dp > 0.0 && dq < 0.0)) {
+        const double t = dp / (dp - dq);
+        b[m][0] = P[0] + t * (Q[0] - P[0]);
+        b[m][1] = P[1] + t * (Q[1] - P[1]);
+        ++m;
+      }
+    }
+    n = m;
+    for (int k = 0; k < n; ++k) {
+      a[k][0] = b[k][0];
+      a[k][1] = b[k][1];
+    }
+  }
+  double area = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double* P = a[k];
+    const double* Q = a[(k + 1) % n];
+    area += P[0] * Q[1] - Q[0] * P[1];
+  }
+  return 0.5 * fabs(area);
+}
+
+// A distant light as its grid sees it: the object-space shadow direction rd
+// (the kernel's rd, up to float32 rounding), its length, and an orthonormal
+// basis (e1, e2) of the plane orthogonal to it. dir: the light's travel
+// direction (world); false: a degenerate direction (no grid).
+struct LightBasis {
+  double rd[3], rlen, e1[3], e2[3];
+};
+__host__ __device__ inline bool light_basis(const double w2o[16], const double dir[3], LightBasis* b) {
+  const double sd[3] = {-dir[0], -dir[1], -dir[2]};
+  xform_dir(w2o, sd, b->rd);
+  b->rlen = norm3(b->rd);
+  if (!(b->rlen > 0.0) || !isfinite(b->rlen)) return false;
+  const double u[3] = {b->rd[0] / b->rlen, b->rd[1] / b->rlen, b->rd[2] / b->rlen};
+  // the axis u is least aligned with (ties: x before y before z)
+  const int ax = fabs(u[0]) <= fabs(u[1]) && fabs(u[0]) <= fabs(u[2]) ? 0 : fabs(u[1]) <= fabs(u[2]) ? 1 : 2;
+  double a[3] = {0, 0, 0};
+  a[ax] = 1.0;
+  cross3(a, u, b->e1);
+  const double l1 = norm3(b->e1);
+  for (int k = 0; k < 3; ++k) b->e1[k] /= l1;
+  cross3(u, b->e1, b->e2);
+  return true;
+}
+// max(scale, |every coordinate of the face|): the grids' length scale starts at 1.
+__host__ __device__ inline double light_face_scale(double scale, const double v[3][3]) {
+  for (int a = 0; a < 3; ++a)
+    for (int k = 0; k < 3; ++k) scale = dmax(scale, fabs(v[a][k]));
+  return scale;
+}
+// One face under one light: false when it faces away from the light (never
+// listed); else its projected vertices q[6] and their bounding box grown by
+// delta (box: u0, u1, v0, v1).
+__host__ __device__ inline bool light_face_box(const LightBasis& b, const double v[3][3], double delta, double q[6],
+                                               double box[4]) {
+  double f1[3], f2[3], c[3], nn[3];
+  for (int k = 0; k < 3; ++k) {
+    f1[k] = v[1][k] - v[0][k];
+    f2[k] = v[2][k] - v[0][k];
+  }
+  cross3(f1, f2, c);
+  for (int k = 0; k < 3; ++k) nn[k] = -c[k];
+  if (never_passes(dot3(b.rd, nn), b.rlen, norm3(nn))) return false;
+  double bu0 = INFINITY, bu1 = -INFINITY, bv0 = INFINITY, bv1 = -INFINITY;
+  for (int a = 0; a < 3; ++a) {
+    const double pu = dot3(v[a], b.e1), pv = dot3(v[a], b.e2);
+    q[2 * a] = pu;
+    q[2 * a + 1] = pv;
+    bu0 = dmin(bu0, pu);
+    bu1 = dmax(bu1, pu);
+    bv0 = dmin(bv0, pv);
+    bv1 = dmax(bv1, pv);
+  }
+  box[0] = bu0 - delta;
+  box[1] = bu1 + delta;
+  box[2] = bv0 - delta;
+  box[3] = bv1 + delta;
+  return true;
+}
+// The grid's header from the bounds of the kept faces' boxes: about `density`
+// cells per listed face, square cells, at most 4096 per side; kept == 0: the
+// empty 1 x 1 grid. off_base / ent_base are the caller's.
+__host__ __device__ inline void light_grid_header(const LightBasis& b, double scale, long long kept, double umin,
+                                                  double umax, double vmin, double vmax, double density,
+                                                  LightGrid* g) {
+  for (int k = 0; k < 3; ++k) {
+    g->e1[k] = (float)b.e1[k];
+    g->e2[k] = (float)b.e2[k];
+  }
+  g->rmax = (float)(100.0 * scale);
+  if (kept == 0) {
+    g->u0 = g->v0 = 0.0f;
+    g->inv_h = 1.0f;
+    g->gu = g->gv = 1;
+    return;
+  }
+  const double du = dmax(umax - umin, 1e-30), dv = dmax(vmax - vmin, 1e-30);
+  double h = sqrt(du * dv / (density * (double)kept));
+  h = dmax(h, dmax(du, dv) / 4096.0);
+  const int cu = (int)ceil(du / h), cv = (int)ceil(dv / h);
+  // the float32 origin / cell size the kernel uses, so host and device agree on
+  // cell edges up to float32 rounding (covered by delta)
+  g->u0 = (float)umin;
+  g->v0 = (float)vmin;
+  g->inv_h = (float)(1.0 / h);
+  g->gu = cu > 4096 ? 4096 : cu < 1 ? 1 : cu;
+  g->gv = cv > 4096 ? 4096 : cv < 1 ? 1 : cv;
+}
+// The cells a face's grown box reaches (rc: c0, c1, r0, r1; empty when c0 > c1
+// or r0 > r1).
+__host__ __device__ inline void light_cell_range(const LightGrid& g, const double box[4], int rc[4]) {
+  const double ih = (double)g.inv_h;
+  const int c0 = (int)floor((box[0] - (double)g.u0) * ih), c1 = (int)floor((box[1] - (double)g.u0) * ih);
+  const int r0 = (int)floor((box[2] - (double)g.v0) * ih), r1 = (int)floor((box[3] - (double)g.v0) * ih);
+  rc[0] = c0 < 0 ? 0 : c0;
+  rc[1] = c1 > g.gu - 1 ? g.gu - 1 : c1;
+  rc[2] = r0 < 0 ? 0 : r0;
+  rc[3] = r1 > g.gv - 1 ? g.gv - 1 : r1;
+}
+// Cell (c, r) grown by delta: a face is listed there when it meets this box.
+__host__ __device__ inline bool light_face_in_cell(const LightGrid& g, const double* q, double delta, int c, int r) {
+  const double ih = (double)g.inv_h;
+  const double cu0 = (double)g.u0 + c / ih, cv0 = (double)g.v0 + r / ih;
+  return tri_meets_box(q, cu0 - delta, cv0 - delta, cu0 + 1.0 / ih + delta, cv0 + 1.0 / ih + delta);
+}
+// The area of cell (c, r) a face's projection covers: a cell's faces are
+// ordered by it, largest first (ties: the lower leaf index first).
+__host__ __device__ inline double light_cell_cover(const LightGrid& g, const double* q, int c, int r) {
+  const double hc = 1.0 / (double)g.inv_h;
+  const double cu0 = (double)g.u0 + c * hc, cv0 = (double)g.v0 + r * hc;
+  return clipped_area(q, cu0, cv0, cu0 + hc, cv0 + hc);
+}
+
+// LTri (rt_common.h) of face v for the shadow direction d (mesh object
+// space, float64): p, q, tv rounded to float32 first, the constants formed
+// from the ROUNDED vectors (u(v0) = 0 up to the float64 sum), so each affine
+// function keeps its zero at the face's vertex.
+__host__ __device__ inline void make_ltri(const double v[3][3], const double d[3], int32_t face, LTri* out) {
+  double e1[3], e2[3], cr[3], nn[3], p[3], q[3], me1[3];
+  for (int k = 0; k < 3; ++k) {
+    e1[k] = v[1][k] - v[0][k];
+    e2[k] = v[2][k] - v[0][k];
+    me1[k] = -e1[k];
+  }
+  cross3(e1, e2, cr);
+  for (int k = 0; k < 3; ++k) nn[k] = -cr[k];
+  const double det = dot3(nn, d);
+  const LTri zero = {};
+  *out = zero;
+  out->id = face;
+  if (!(det >= 1e-6)) {  // geom.nim:306: never passes for this light
+    out->cu = out->cv = out->ct = -1.0f;
+    return;
+  }
+  cross3(d, e2, p);
+  cross3(d, me1, q);
+  double pr[3], qr[3], tr[3];
+  for (int k = 0; k < 3; ++k) {
+    out->p[k] = (float)(p[k] / det);
+    out->q[k] = (float)(q[k] / det);
+    out->tv[k] = (float)(nn[k] / -det);
+    pr[k] = out->p[k];
+    qr[k] = out->q[k];
+    tr[k] = out->tv[k];
+  }
+  out->cu = (float)-dot3(pr, v[0]);
+  out->cv = (float)-dot3(qr, v[0]);
+  out->ct = (float)-dot3(tr, v[0]);
+}
+// The slot every light's record array starts from: a face that can never
+// pass (u = v = t = -1). An all-zero record would read as a hit at t = 0.
+__host__ __device__ inline LTri culled_ltri() {
+  LTri c = {};
+  c.cu = c.cv = c.ct = -1.0f;
+  c.id = -1;
+  return c;
+}
+
 // Camera-ray bins of one face (build_pixel_bins): the face's projected
 // vertices in pixel coordinates (q[6]) and its pixel rectangle (rect[4]:
 // x0, x1, y0, y1; x0 = -1: the face gets no bin). Returns false when a vertex

@@ -232,6 +232,17 @@ int rt_multi_set_camera(rt_multi* m, const double camera_to_world[16], double fo
   return RT_OK;
 }
 
+int rt_multi_set_lights(rt_multi* m, const rt_light_desc* lights, int32_t num_lights) {
+  if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  CurrentDevice keep;
+  for (rt_scene* s : m->scene) {
+    const int rc = rt_scene_set_lights(s, lights, num_lights);
+    if (rc) return rc;
+  }
+  return RT_OK;
+}
+
 int rt_multi_destroy(rt_multi* m) {
   if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
   {

@@ -28,6 +28,7 @@
 #include "rt_bvh.h"
 #include "rt_common.h"
 #include "rt_frame.h"
+#include "rt_lights_gpu.h"
 #include "rt_query.h"
 
 using namespace rtmi;
@@ -158,42 +159,6 @@ inline int slot_lg_for(int w, int h) {
   return lg;
 }
 
-// LTri (rt_common.h) of face v for the shadow direction d (mesh object
-// space, float64): p, q, tv rounded to float32 first, the constants formed
-// from the ROUNDED vectors (u(v0) = 0 up to the float64 sum), so each affine
-// function keeps its zero at the face's vertex.
-static void make_ltri(const double v[3][3], const double d[3], int32_t face, LTri* out) {
-  double e1[3], e2[3], cr[3], nn[3], p[3], q[3], me1[3];
-  for (int k = 0; k < 3; ++k) {
-    e1[k] = v[1][k] - v[0][k];
-    e2[k] = v[2][k] - v[0][k];
-    me1[k] = -e1[k];
-  }
-  rtmi::bg::cross3(e1, e2, cr);
-  for (int k = 0; k < 3; ++k) nn[k] = -cr[k];
-  const double det = rtmi::bg::dot3(nn, d);
-  std::memset(out, 0, sizeof *out);
-  out->id = face;
-  if (!(det >= 1e-6)) {  // geom.nim:306: never passes for this light
-    out->cu = out->cv = out->ct = -1.0f;
-    return;
-  }
-  rtmi::bg::cross3(d, e2, p);
-  rtmi::bg::cross3(d, me1, q);
-  double pr[3], qr[3], tr[3];
-  for (int k = 0; k < 3; ++k) {
-    out->p[k] = (float)(p[k] / det);
-    out->q[k] = (float)(q[k] / det);
-    out->tv[k] = (float)(nn[k] / -det);
-    pr[k] = out->p[k];
-    qr[k] = out->q[k];
-    tr[k] = out->tv[k];
-  }
-  out->cu = (float)-rtmi::bg::dot3(pr, v[0]);
-  out->cv = (float)-rtmi::bg::dot3(qr, v[0]);
-  out->ct = (float)-rtmi::bg::dot3(tr, v[0]);
-}
-
 struct rt_scene {
   std::mutex mu;
   int device = 0;
@@ -294,6 +259,22 @@ struct rt_scene {
   std::vector<LightGridHost> grid_host;  // per light: the cell lists + face boxes the shadow lists gather from
   std::vector<SkipPlane> skip_planes;
   bool skippable = false;
+  // rt_scene_set_lights: the current lights, and what build_lights reads of
+  // the objects. After a relight only each grid's header (grid_occ[].g,
+  // grid_host[].g) and entry count (grid_nent, padding included) are on the
+  // host: the bulky mirrors (grid_host[].off / ent / box, grid_occ[].sat) are
+  // stale until a test hook asks for them (refresh_host_lists).
+  std::vector<rt_light_desc> light_desc;
+  struct ObjMeta {
+    int32_t type;
+    double reflection, o2w[16], w2o[16];
+  };
+  std::vector<ObjMeta> obj_meta;
+  std::vector<int64_t> grid_nent;
+  bool mirrors_stale = false;
+  double bin_scale = 0.0;          // the grids' length scale of bin_dev (0: not yet reduced)
+  bool relight_timed = false;      // time the device builder's passes (rtmi_test_relight_passes)
+  float relight_ms[6] = {};        // the last timed relight's passes
   // camera-dependent data of the float32 kernels (rt_frame.h): rebuilt on
   // the device by every render call; only the buffers outlive a call
   DevBuf<DevBinTri> bin_dev;       // the binned mesh's faces (float64, leaf order)
@@ -556,6 +537,32 @@ int32_t classify_xf(const double* w2o, const double* o2w) {
   return XF_TRANSLATE;
 }
 
+// The lights' records of the parity kernels (DevLight) and of the float32
+// kernels (FLight): rt_scene_create and rt_scene_set_lights form the same.
+template <class R>
+void fill_lights(const rt_light_desc* src, int32_t n, std::vector<DevLight<R>>& lights) {
+  lights.assign((size_t)n, DevLight<R>{});
+  for (int i = 0; i < n; ++i) {
+    const rt_light_desc& s = src[i];
+    DevLight<R>& l = lights[(size_t)i];
+    // color * intensity, computed in float64 like light.nim:50,57
+    for (int k = 0; k < 3; ++k) l.ci[k] = (R)(s.color[k] * s.intensity);
+    for (int k = 0; k < 3; ++k) l.v[k] = (R)(s.type == RT_POINT_LIGHT ? s.pos[k] : s.dir[k]);
+    l.type = s.type == RT_POINT_LIGHT ? LIGHT_POINT : LIGHT_DISTANT;
+  }
+}
+void fill_fast_lights(const rt_light_desc* src, int32_t n, std::vector<FLight>& fl) {
+  fl.assign((size_t)n, FLight{});
+  for (int i = 0; i < n; ++i) {
+    const rt_light_desc& s = src[i];
+    fl[(size_t)i].type = s.type == RT_POINT_LIGHT ? LIGHT_POINT : LIGHT_DISTANT;
+    for (int k = 0; k < 3; ++k) {
+      fl[(size_t)i].ci[k] = (float)(s.color[k] * s.intensity);
+      fl[(size_t)i].v[k] = (float)(s.type == RT_POINT_LIGHT ? s.pos[k] : s.dir[k]);
+    }
+  }
+}
+
 template <class R>
 void fill_precision(const rt_scene_desc* d, const std::vector<std::vector<double>>& normals,
                     const std::vector<BvhResult>& bvhs, const std::vector<int32_t>& node_base,
@@ -585,15 +592,7 @@ void fill_precision(const rt_scene_desc* d, const std::vector<std::vector<double
     o.mesh = s.type == RT_MESH ? s.mesh : 0;
     o.xf = classify_xf(s.world_to_object, s.object_to_world);
   }
-  lights.assign((size_t)d->num_lights, DevLight<R>{});
-  for (int i = 0; i < d->num_lights; ++i) {
-    const rt_light_desc& s = d->lights[i];
-    DevLight<R>& l = lights[(size_t)i];
-    // color * intensity, computed in float64 like light.nim:50,57
-    for (int k = 0; k < 3; ++k) l.ci[k] = (R)(s.color[k] * s.intensity);
-    for (int k = 0; k < 3; ++k) l.v[k] = (R)(s.type == RT_POINT_LIGHT ? s.pos[k] : s.dir[k]);
-    l.type = s.type == RT_POINT_LIGHT ? LIGHT_POINT : LIGHT_DISTANT;
-  }
+  fill_lights<R>(d->lights, d->num_lights, lights);
   meshes.assign((size_t)d->num_meshes, DevMesh<R>{});
   int64_t total = 0;
   for (int m = 0; m < d->num_meshes; ++m) total += d->meshes[m].num_faces;
@@ -684,15 +683,356 @@ void fill_fast_records(const rt_scene_desc* d, const std::vector<DevMesh<float>>
     fm[m].root = dm[m].root;
     fm[m].normal_base = dm[m].normal_base;
   }
-  fl.assign((size_t)d->num_lights, FLight{});
-  for (int i = 0; i < d->num_lights; ++i) {
-    const rt_light_desc& s = d->lights[i];
-    fl[(size_t)i].type = s.type == RT_POINT_LIGHT ? LIGHT_POINT : LIGHT_DISTANT;
-    for (int k = 0; k < 3; ++k) {
-      fl[(size_t)i].ci[k] = (float)(s.color[k] * s.intensity);
-      fl[(size_t)i].v[k] = (float)(s.type == RT_POINT_LIGHT ? s.pos[k] : s.dir[k]);
+  fill_fast_lights(d->lights, d->num_lights, fl);
+}
+
+// Everything of a scene that depends on its lights. rt_scene_create and
+// rt_scene_set_lights both build one (build_lights) and hand it to the scene
+// (adopt_lights), so the two cannot drift apart; after the hand-over it holds
+// the scene's previous state, for release().
+struct LightState {
+  std::vector<rt_light_desc> desc;
+  int32_t has_point_light = 0;
+  std::vector<float> h_light_vy;
+  DevBuf<FLight> f32_lights;
+  DevBuf<DevLight<double>> f64_lights;
+  DevBuf<LightGrid> grids;
+  DevBuf<LTri> lrec, grec;
+  int64_t lrec_ntri = 0;
+  uint32_t lrec_mask = 0;
+  DevBuf<int32_t> grid_off, grid_ent;
+  bool has_grids = false;
+  std::vector<GridOcc> grid_occ;
+  std::vector<LightGridHost> grid_host;
+  std::vector<int64_t> grid_nent;
+  bool mirrors_stale = false;
+  std::vector<SkipPlane> skip_planes;
+  bool skippable = false;
+  int32_t lean64_plane = -1;
+  DevBuf<int32_t> sat_dev;
+  int64_t sat_off[8] = {};
+  DevBuf<LightGrid> obj_grids;
+  DevBuf<unsigned long long> obj_grid_mask;
+  unsigned long long obj_off_grid = 0;
+  bool has_obj_grids = false;
+  float ms[6] = {};
+  void release() {
+    f32_lights.release();
+    f64_lights.release();
+    grids.release();
+    lrec.release();
+    grec.release();
+    grid_off.release();
+    grid_ent.release();
+    sat_dev.release();
+    obj_grids.release();
+    obj_grid_mask.release();
+  }
+};
+
+// The distant lights' mesh grids, records and prefix sums by the host
+// builders (rt_bins.cpp): rt_scene_create's path.
+int mesh_grids_host(rt_scene* s, const rt_light_desc* lights, int32_t nl, LightState* L, bool* any_out) {
+  const int64_t nnodes = s->num_nodes, ntri = s->num_triangles;
+  int rc;
+  std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
+  std::vector<int32_t> goff, gent;
+  bool any = false;
+  for (int li = 0; s->binnable && li < nl; ++li) {
+    if (lights[li].type == RT_POINT_LIGHT) continue;
+    LightGridHost lg;
+    const char* why = "";
+    if (!build_light_grid(s->bin_tris, s->mesh_w2o, lights[li].dir, &lg, &why)) continue;
+    if ((int64_t)goff.size() + (int64_t)lg.off.size() > INT32_MAX ||
+        (int64_t)gent.size() + (int64_t)lg.ent.size() > INT32_MAX)
+      break;
+    lg.g.off_base = (int32_t)goff.size();
+    lg.g.ent_base = (int32_t)gent.size();
+    goff.insert(goff.end(), lg.off.begin(), lg.off.end());
+    gent.insert(gent.end(), lg.ent.begin(), lg.ent.end());
+    gh[(size_t)li] = lg.g;
+    grid_occupancy(lg, &L->grid_occ[(size_t)li]);
+    L->grid_nent[(size_t)li] = (int64_t)lg.ent.size();
+    L->grid_host[(size_t)li] = std::move(lg);
+    L->grid_occ[(size_t)li].lists = &L->grid_host[(size_t)li];
+    any = true;
+  }
+  *any_out = any;
+  if (!any) return RT_OK;
+  if ((rc = L->grids.upload(gh)) || (rc = L->grid_off.upload(goff)) || (rc = L->grid_ent.upload(gent))) return rc;
+  // the shadow-test records of the lights with a grid (the float32
+  // kernels' every shadow ray to such a light tests these, on every path)
+  const size_t nt = (size_t)ntri;  // indexed like the TriFast records: byte offset / 64 - nnodes
+  // every slot starts as the culled sentinel make_ltri writes for a face
+  // that can never pass (u = v = t = -1): an all-zero record would read
+  // as a hit at t = 0 (u = v = 0 passes min(u, v, 1-u-v) >= 0) if a
+  // future path read a slot of another mesh's face or of a light with
+  // no grid
+  const LTri culled = bg::culled_ltri();
+  std::vector<LTri> lr((size_t)nl * nt, culled);
+  for (int li = 0; li < nl; ++li) {
+    if (gh[(size_t)li].gu <= 0) continue;
+    const double* dir = lights[li].dir;
+    double sd[3], ld[3];
+    for (int k = 0; k < 3; ++k) sd[k] = -dir[k];
+    bg::xform_dir(s->mesh_w2o, sd, ld);  // the shadow direction in the mesh's object space
+    parallel_for((int64_t)s->bin_tris.size(), [&](int64_t b, int64_t e) {
+      for (int64_t i = b; i < e; ++i) {
+        const BinTri& t = s->bin_tris[(size_t)i];
+        const int64_t slot = (int64_t)t.rec / (int64_t)sizeof(TriFast) - nnodes;
+        bg::make_ltri(t.v, ld, t.face, &lr[(size_t)li * nt + (size_t)slot]);
+      }
+    });
+  }
+  if ((rc = L->lrec.upload(lr))) return rc;
+  // the cell-ordered copy: entry e of light li's grid -> its face's record
+  std::vector<LTri> gr(gent.size(), culled);
+  for (int li = 0; li < nl; ++li) {
+    if (gh[(size_t)li].gu <= 0) continue;
+    const size_t e0 = (size_t)gh[(size_t)li].ent_base, ne = L->grid_host[(size_t)li].ent.size();
+    parallel_for((int64_t)ne, [&](int64_t b, int64_t e) {
+      for (int64_t k = b; k < e; ++k) {
+        const int64_t slot = (int64_t)gent[e0 + (size_t)k] / (int64_t)sizeof(TriFast) - nnodes;
+        gr[e0 + (size_t)k] = lr[(size_t)li * nt + (size_t)slot];
+      }
+    });
+  }
+  if ((rc = L->grec.upload(gr))) return rc;
+  // the occupancy prefix sums the per-call shadow skips read (rt_frame.h)
+  std::vector<int32_t> sat;
+  for (int li = 0; li < std::min(8, nl); ++li) {
+    L->sat_off[li] = (int64_t)sat.size();
+    sat.insert(sat.end(), L->grid_occ[(size_t)li].sat.begin(), L->grid_occ[(size_t)li].sat.end());
+  }
+  if (sat.empty()) sat.push_back(0);
+  return L->sat_dev.upload(sat);
+}
+
+// The same arrays, byte for byte, by the device builder (rt_lights_gpu.hip)
+// from the resident faces: rt_scene_set_lights' path. Only each grid's header
+// and entry count come back to the host.
+int mesh_grids_device(rt_scene* s, const rt_light_desc* lights, int32_t nl, LightState* L, bool* any_out) {
+  *any_out = false;
+  if (!s->binnable) return RT_OK;
+  bool distant = false;
+  for (int li = 0; li < nl; ++li) distant = distant || lights[li].type != RT_POINT_LIGHT;
+  if (!distant) return RT_OK;
+  const int64_t ntri = s->num_triangles;
+  const auto hip_fail = [](int e) {
+    return fail(e == (int)hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_DEVICE, "light grid build: %s",
+                hipGetErrorString((hipError_t)e));
+  };
+  int rc;
+  if (!(s->bin_scale > 0.0)) {  // the faces do not change: reduced once per scene
+    double sc = 1.0;
+    if (int e = rtmi_lights_scale(s->bin_dev.p, (int64_t)s->bin_tris.size(), &sc, s->stream)) return hip_fail(e);
+    s->bin_scale = sc;
+  }
+  std::vector<LightGridDev> dg((size_t)nl);
+  for (LightGridDev& g : dg) std::memset(&g, 0, sizeof g);
+  struct FreeGrids {
+    std::vector<LightGridDev>& v;
+    ~FreeGrids() {
+      for (LightGridDev& g : v) rtmi_lights_free(&g);
+    }
+  } free_grids{dg};
+  if ((rc = L->lrec.alloc((size_t)nl * (size_t)ntri))) return rc;
+  if (int e = rtmi_lights_fill_culled(L->lrec.p, (int64_t)nl * ntri, s->stream)) return hip_fail(e);
+  const bool timed = s->relight_timed;
+  std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
+  int64_t noff = 0, nent = 0;
+  bool any = false;
+  for (int li = 0; li < nl; ++li) {
+    if (lights[li].type == RT_POINT_LIGHT) continue;
+    LightGridJob job;
+    job.tris = s->bin_dev.p;
+    job.n = (int64_t)s->bin_tris.size();
+    job.rec0 = s->bin_tris[0].rec;
+    std::memcpy(job.w2o, s->mesh_w2o, sizeof job.w2o);
+    for (int k = 0; k < 3; ++k) job.dir[k] = lights[li].dir[k];
+    job.scale = s->bin_scale;
+    job.density = light_grid_density();
+    job.nnodes = s->num_nodes;
+    job.ntri = ntri;
+    job.lrec = L->lrec.p + (size_t)li * (size_t)ntri;
+    LightGridDev& g = dg[(size_t)li];
+    if (int e = rtmi_light_grid_build(&job, &g, timed ? 1 : 0, s->stream)) return hip_fail(e);
+    if (!g.built) continue;
+    if (noff + g.noff > INT32_MAX || nent + g.nent > INT32_MAX) {
+      // as the host: this light and every later one go without a grid
+      if (int e = rtmi_lights_fill_culled(job.lrec, ntri, s->stream)) return hip_fail(e);
+      rtmi_lights_free(&g);
+      g.built = 0;
+      break;
+    }
+    g.g.off_base = (int32_t)noff;
+    g.g.ent_base = (int32_t)nent;
+    noff += g.noff;
+    nent += g.nent;
+    gh[(size_t)li] = g.g;
+    L->grid_occ[(size_t)li].g = g.g;
+    L->grid_host[(size_t)li].g = g.g;
+    L->grid_nent[(size_t)li] = g.nent;
+    for (int k = 0; k < 6; ++k) L->ms[k] += g.ms[k];
+    any = true;
+  }
+  *any_out = any;
+  if (!any) {
+    L->lrec.release();
+    return RT_OK;
+  }
+  L->mirrors_stale = true;
+  if ((rc = L->grids.upload(gh)) || (rc = L->grid_off.alloc((size_t)noff)) || (rc = L->grid_ent.alloc((size_t)nent)) ||
+      (rc = L->grec.alloc((size_t)nent)))
+    return rc;
+  int64_t nsat = 0;
+  for (int li = 0; li < std::min(8, nl); ++li) {
+    L->sat_off[li] = nsat;
+    if (dg[(size_t)li].built) nsat += dg[(size_t)li].nsat;
+  }
+  if ((rc = L->sat_dev.alloc((size_t)std::max<int64_t>(1, nsat)))) return rc;
+  if (nsat == 0) HIP_TRY(hipMemset(L->sat_dev.p, 0, sizeof(int32_t)));
+  for (int li = 0; li < nl; ++li) {
+    const LightGridDev& g = dg[(size_t)li];
+    if (!g.built) continue;
+    HIP_TRY(hipMemcpy(L->grid_off.p + g.g.off_base, g.off, (size_t)g.noff * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(L->grid_ent.p + g.g.ent_base, g.ent, (size_t)g.nent * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(L->grec.p + g.g.ent_base, g.grec, (size_t)g.nent * sizeof(LTri), hipMemcpyDeviceToDevice));
+    if (li < 8)
+      HIP_TRY(hipMemcpy(L->sat_dev.p + L->sat_off[li], g.sat, (size_t)g.nsat * sizeof(int32_t), hipMemcpyDeviceToDevice));
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return RT_OK;
+}
+
+// Builds the scene's light-dependent state for `lights` into *L; reads only
+// what does not depend on the lights (the faces, the objects, the BVH sizes).
+// device: the mesh light grids by the device builder, else by the host's.
+int build_lights(rt_scene* s, const rt_light_desc* lights, int32_t nl, bool device, LightState* L) {
+  int rc;
+  L->desc.assign(lights, lights + nl);
+  for (int i = 0; i < nl; ++i)
+    if (lights[i].type == RT_POINT_LIGHT) L->has_point_light = 1;
+  {
+    std::vector<FLight> fl;
+    std::vector<DevLight<double>> dl;
+    fill_fast_lights(lights, nl, fl);
+    fill_lights<double>(lights, nl, dl);
+    for (const FLight& q : fl) L->h_light_vy.push_back(q.v[1]);
+    if ((rc = L->f32_lights.upload(fl)) || (rc = L->f64_lights.upload(dl))) return rc;
+  }
+  const int nobj = (int)s->obj_meta.size();
+  if (s->shadow_mesh >= 0) {  // light grids of the distant lights over the only mesh object
+    L->grid_occ.assign((size_t)nl, GridOcc{});
+    L->grid_host.assign((size_t)nl, LightGridHost{});
+    L->grid_nent.assign((size_t)nl, 0);
+    bool any = false;
+    if ((rc = device ? mesh_grids_device(s, lights, nl, L, &any) : mesh_grids_host(s, lights, nl, L, &any))) return rc;
+    if (any) {
+      L->has_grids = true;
+      L->lrec_ntri = s->num_triangles;
+      for (int li = 0; li < nl && li < 32; ++li)
+        if (L->grid_occ[(size_t)li].g.gu > 0) L->lrec_mask |= 1u << li;
+      // shadow skips: every other object a plane
+      L->skippable = true;
+      for (int i = 0; i < nobj; ++i) {
+        const rt_scene::ObjMeta& o = s->obj_meta[(size_t)i];
+        if (i == s->shadow_mesh) continue;
+        SkipPlane sp;
+        L->skippable = L->skippable && o.type == RT_PLANE;
+        std::memcpy(sp.o2w, o.o2w, sizeof sp.o2w);
+        std::memcpy(sp.w2o, o.w2o, sizeof sp.w2o);
+        L->skip_planes.push_back(sp);
+      }
+      if (!L->skippable) L->skip_planes.clear();
+      // k_render_px64's lean samples: one mesh + one non-reflective plane,
+      // distant lights only (each with a skip bit)
+      if (L->skippable && nobj == 2 && nl >= 1 && nl <= 8) {
+        const int pl = 1 - s->shadow_mesh;
+        bool ok = s->obj_meta[(size_t)pl].type == RT_PLANE && !(s->obj_meta[(size_t)pl].reflection > 0.0);
+        for (int li = 0; li < nl; ++li) ok = ok && lights[li].type != RT_POINT_LIGHT;
+        if (ok) L->lean64_plane = pl;
+      }
     }
   }
+  if (s->objbins) {  // the object light grids (rt_bins.h): at most 64 boxes, built on the host
+    std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
+    std::vector<unsigned long long> gm;
+    bool any = false;
+    for (int li = 0; li < nl; ++li) {
+      if (lights[li].type == RT_POINT_LIGHT) continue;
+      ObjGridHost og;
+      const char* why = "";
+      if (!build_object_light_grid(s->obj_boxes, lights[li].dir, &og, &why)) continue;
+      if ((int64_t)gm.size() + (int64_t)og.masks.size() > INT32_MAX) break;
+      og.g.off_base = (int32_t)gm.size();
+      gm.insert(gm.end(), og.masks.begin(), og.masks.end());
+      gh[(size_t)li] = og.g;
+      L->obj_off_grid = og.off_grid;  // the same set (the unbounded objects) for every light
+      any = true;
+    }
+    if (any) {
+      if ((rc = L->obj_grids.upload(gh)) || (rc = L->obj_grid_mask.upload(gm))) return rc;
+      L->has_obj_grids = true;
+    }
+  }
+  return RT_OK;
+}
+
+// Hands *L to the scene; *L takes the scene's previous state.
+void adopt_lights(rt_scene* s, LightState* L) {
+  s->nlight = (int32_t)L->desc.size();
+  std::swap(s->light_desc, L->desc);
+  s->has_point_light = L->has_point_light;
+  s->f32_subset = (s->f32_subset & ~(unsigned)SUB_POINT) | (s->has_point_light ? (unsigned)SUB_POINT : 0u);
+  std::swap(s->h_light_vy, L->h_light_vy);
+  std::swap(s->f32.lights, L->f32_lights);
+  std::swap(s->f64.lights, L->f64_lights);
+  std::swap(s->grids, L->grids);
+  std::swap(s->lrec, L->lrec);
+  std::swap(s->grec, L->grec);
+  s->lrec_ntri = L->lrec_ntri;
+  s->lrec_mask = L->lrec_mask;
+  std::swap(s->grid_off, L->grid_off);
+  std::swap(s->grid_ent, L->grid_ent);
+  s->has_grids = L->has_grids;
+  std::swap(s->grid_occ, L->grid_occ);
+  std::swap(s->grid_host, L->grid_host);
+  // the lists point into grid_host, which moved with its buffer
+  for (size_t li = 0; li < s->grid_occ.size(); ++li)
+    s->grid_occ[li].lists = s->grid_occ[li].lists ? &s->grid_host[li] : nullptr;
+  std::swap(s->grid_nent, L->grid_nent);
+  s->mirrors_stale = L->mirrors_stale;
+  std::swap(s->skip_planes, L->skip_planes);
+  s->skippable = L->skippable;
+  s->lean64_plane = L->lean64_plane;
+  std::swap(s->sat_dev, L->sat_dev);
+  std::memcpy(s->sat_off, L->sat_off, sizeof s->sat_off);
+  std::swap(s->obj_grids, L->obj_grids);
+  std::swap(s->obj_grid_mask, L->obj_grid_mask);
+  s->obj_off_grid = L->obj_off_grid;
+  s->has_obj_grids = L->has_obj_grids;
+  std::memcpy(s->relight_ms, L->ms, sizeof s->relight_ms);
+}
+
+// The bulky host mirrors of the light grids (cell lists, face boxes, prefix
+// sums) after a relight, for the test hooks that read them: the host builder
+// forms what the device built (rtmi_test_relight_diff checks that it does).
+void refresh_host_lists(rt_scene* s) {
+  if (!s->mirrors_stale) return;
+  for (size_t li = 0; li < s->grid_occ.size(); ++li) {
+    const LightGrid kept = s->grid_occ[li].g;
+    if (kept.gu <= 0) continue;
+    LightGridHost lg;
+    const char* why = "";
+    if (!build_light_grid(s->bin_tris, s->mesh_w2o, s->light_desc[li].dir, &lg, &why)) continue;
+    lg.g.off_base = kept.off_base;
+    lg.g.ent_base = kept.ent_base;
+    grid_occupancy(lg, &s->grid_occ[li]);
+    s->grid_host[li] = std::move(lg);
+    s->grid_occ[li].lists = &s->grid_host[li];
+  }
+  s->mirrors_stale = false;
 }
 
 }  // namespace
@@ -843,9 +1183,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
       }
     if (n_mesh_obj != 1) s->shadow_mesh = -1;
   }
-  s->nlight = d->num_lights;
-  for (int i = 0; i < d->num_lights; ++i)
-    if (d->lights[i].type == RT_POINT_LIGHT) s->has_point_light = 1;
   s->nmesh = d->num_meshes;
   s->any_reflective = any_reflective;
   // scene features -> the float32 kernel specialisation (rt_kernels_f32_part.hip)
@@ -857,8 +1194,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     if (ob.type == RT_MESH) s->f32_subset |= SUB_MESH;
     if (classify_xf(ob.world_to_object, ob.object_to_world) == XF_GENERAL) s->f32_subset |= SUB_XF_GENERAL;
   }
-  if (s->has_point_light) s->f32_subset |= SUB_POINT;
-  if (any_reflective) s->f32_subset |= SUB_REFLECT;
+  if (any_reflective) s->f32_subset |= SUB_REFLECT;  // (SUB_POINT: adopt_lights)
   s->fov = d->fov;
   std::memcpy(s->c2w, d->camera_to_world, sizeof s->c2w);
   std::memcpy(s->bg, d->bg_color, sizeof s->bg);
@@ -911,10 +1247,9 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<FLight> fl;
     fill_fast_records(d, m, fo, fx, fm, fl);
     for (const FObj& q : fo) s->h_obj_ty.push_back(q.t[1]);
-    for (const FLight& q : fl) s->h_light_vy.push_back(q.v[1]);
     int rc;
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
-        (rc = s->f32.lights.upload(fl)) || (rc = s->f32.normals.upload(n)))
+        (rc = s->f32.normals.upload(n)))
       return rc;
     mark("fp32 upload");
   }
@@ -926,7 +1261,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     fill_precision<double>(d, normals, bvhs, node_base, aabbs, o, l, m, nullptr, n);
     mark("fp64 records");
     int rc;
-    if ((rc = s->f64.objects.upload(o)) || (rc = s->f64.lights.upload(l)) || (rc = s->f64.meshes.upload(m)) ||
+    if ((rc = s->f64.objects.upload(o)) || (rc = s->f64.meshes.upload(m)) ||
         (rc = s->f64.normals.upload(n)))
       return rc;
   }
@@ -1002,111 +1337,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
         s->mesh_hi[k] = aabbs[(size_t)m][3 + k];
       }
     }
-    // light grids of the distant lights
-    std::vector<LightGrid> gh((size_t)std::max(1, d->num_lights), LightGrid{});
-    s->grid_occ.assign((size_t)d->num_lights, GridOcc{});
-    s->grid_host.assign((size_t)d->num_lights, LightGridHost{});
-    std::vector<int32_t> goff, gent;
-    bool any = false;
-    for (int li = 0; s->binnable && li < d->num_lights; ++li) {
-      if (d->lights[li].type == RT_POINT_LIGHT) continue;
-      LightGridHost lg;
-      const char* why = "";
-      if (!build_light_grid(s->bin_tris, s->mesh_w2o, d->lights[li].dir, &lg, &why)) continue;
-      if ((int64_t)goff.size() + (int64_t)lg.off.size() > INT32_MAX ||
-          (int64_t)gent.size() + (int64_t)lg.ent.size() > INT32_MAX)
-        break;
-      lg.g.off_base = (int32_t)goff.size();
-      lg.g.ent_base = (int32_t)gent.size();
-      goff.insert(goff.end(), lg.off.begin(), lg.off.end());
-      gent.insert(gent.end(), lg.ent.begin(), lg.ent.end());
-      gh[(size_t)li] = lg.g;
-      grid_occupancy(lg, &s->grid_occ[(size_t)li]);
-      s->grid_host[(size_t)li] = std::move(lg);
-      s->grid_occ[(size_t)li].lists = &s->grid_host[(size_t)li];
-      any = true;
-    }
-    if (any) {
-      if ((rc = s->grids.upload(gh)) || (rc = s->grid_off.upload(goff)) || (rc = s->grid_ent.upload(gent))) return rc;
-      s->has_grids = true;
-      // the shadow-test records of the lights with a grid (the float32
-      // kernels' every shadow ray to such a light tests these, on every path)
-      {
-        const size_t nt = (size_t)ntri;  // indexed like the TriFast records: byte offset / 64 - nnodes
-        // every slot starts as the culled sentinel make_ltri writes for a face
-        // that can never pass (u = v = t = -1): an all-zero record would read
-        // as a hit at t = 0 (u = v = 0 passes min(u, v, 1-u-v) >= 0) if a
-        // future path read a slot of another mesh's face or of a light with
-        // no grid
-        LTri culled;
-        std::memset(&culled, 0, sizeof culled);
-        culled.cu = culled.cv = culled.ct = -1.0f;
-        culled.id = -1;
-        std::vector<LTri> lr((size_t)d->num_lights * nt, culled);
-        for (int li = 0; li < d->num_lights; ++li) {
-          if (gh[(size_t)li].gu <= 0) continue;
-          const double* dir = d->lights[li].dir;
-          double sd[3], ld[3];
-          for (int k = 0; k < 3; ++k) sd[k] = -dir[k];
-          bg::xform_dir(s->mesh_w2o, sd, ld);  // the shadow direction in the mesh's object space
-          parallel_for((int64_t)nt, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; ++i) {
-              const BinTri& t = s->bin_tris[(size_t)i];
-              const int64_t slot = (int64_t)t.rec / (int64_t)sizeof(TriFast) - nnodes;
-              make_ltri(t.v, ld, t.face, &lr[(size_t)li * nt + (size_t)slot]);
-            }
-          });
-        }
-        if ((rc = s->lrec.upload(lr))) return rc;
-        s->lrec_ntri = (int64_t)nt;
-        // the cell-ordered copy: entry e of light li's grid -> its face's record
-        std::vector<LTri> gr(gent.size(), culled);
-        for (int li = 0; li < d->num_lights; ++li) {
-          if (gh[(size_t)li].gu <= 0) continue;
-          const LightGridHost& lg = s->grid_host[(size_t)li];
-          const size_t e0 = (size_t)gh[(size_t)li].ent_base, ne = lg.ent.size();
-          parallel_for((int64_t)ne, [&](int64_t b, int64_t e) {
-            for (int64_t k = b; k < e; ++k) {
-              const int64_t slot = (int64_t)gent[e0 + (size_t)k] / (int64_t)sizeof(TriFast) - nnodes;
-              gr[e0 + (size_t)k] = lr[(size_t)li * nt + (size_t)slot];
-            }
-          });
-        }
-        if ((rc = s->grec.upload(gr))) return rc;
-        for (int li = 0; li < d->num_lights && li < 32; ++li)
-          if (gh[(size_t)li].gu > 0) s->lrec_mask |= 1u << li;
-      }
-      // shadow skips: every other object a plane
-      s->skippable = true;
-      for (int i = 0; i < d->num_objects; ++i) {
-        const rt_object_desc& o = d->objects[i];
-        if (i == s->shadow_mesh) continue;
-        SkipPlane sp;
-        s->skippable = s->skippable && o.type == RT_PLANE;
-        std::memcpy(sp.o2w, o.object_to_world, sizeof sp.o2w);
-        std::memcpy(sp.w2o, o.world_to_object, sizeof sp.w2o);
-        s->skip_planes.push_back(sp);
-      }
-      if (!s->skippable) s->skip_planes.clear();
-      // k_render_px64's lean samples: one mesh + one non-reflective plane,
-      // distant lights only (each with a skip bit)
-      s->lean64_plane = -1;
-      if (s->skippable && s->shadow_mesh >= 0 && d->num_objects == 2 && d->num_lights >= 1 && d->num_lights <= 8) {
-        const int pl = 1 - s->shadow_mesh;
-        bool ok = d->objects[pl].type == RT_PLANE && !(d->objects[pl].reflection > 0.0);
-        for (int li = 0; li < d->num_lights; ++li) ok = ok && d->lights[li].type != RT_POINT_LIGHT;
-        if (ok) s->lean64_plane = pl;
-      }
-      // the occupancy prefix sums the per-call shadow skips read (rt_frame.h)
-      std::vector<int32_t> sat;
-      for (int li = 0; li < std::min(8, d->num_lights); ++li) {
-        s->sat_off[li] = (int64_t)sat.size();
-        sat.insert(sat.end(), s->grid_occ[(size_t)li].sat.begin(), s->grid_occ[(size_t)li].sat.end());
-      }
-      if (sat.empty()) sat.push_back(0);
-      if ((rc = s->sat_dev.upload(sat))) return rc;
-    }
-    mark("light grids");
   }
   if (d->num_objects >= 4 && d->num_objects <= 64) {  // object bins (rt_bins.h)
     s->obj_boxes.assign((size_t)d->num_objects, ObjBox{});
@@ -1148,27 +1378,27 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
       ob[(size_t)i].pad = 0;
     }
     if ((rc = s->objbox_dev.upload(ob))) return rc;
-    std::vector<LightGrid> gh((size_t)std::max(1, d->num_lights), LightGrid{});
-    std::vector<unsigned long long> gm;
-    bool any = false;
-    for (int li = 0; li < d->num_lights; ++li) {
-      if (d->lights[li].type == RT_POINT_LIGHT) continue;
-      ObjGridHost og;
-      const char* why = "";
-      if (!build_object_light_grid(s->obj_boxes, d->lights[li].dir, &og, &why)) continue;
-      if ((int64_t)gm.size() + (int64_t)og.masks.size() > INT32_MAX) break;
-      og.g.off_base = (int32_t)gm.size();
-      gm.insert(gm.end(), og.masks.begin(), og.masks.end());
-      gh[(size_t)li] = og.g;
-      s->obj_off_grid = og.off_grid;  // the same set (the unbounded objects) for every light
-      any = true;
-    }
-    if (any) {
-      if ((rc = s->obj_grids.upload(gh)) || (rc = s->obj_grid_mask.upload(gm))) return rc;
-      s->has_obj_grids = true;
-    }
     mark("object bins");
   }
+  // everything that depends on the lights (rt_scene_set_lights replaces it)
+  s->num_triangles = ntri;
+  s->num_nodes = nnodes;
+  s->obj_meta.resize((size_t)d->num_objects);
+  for (int i = 0; i < d->num_objects; ++i) {
+    rt_scene::ObjMeta& om = s->obj_meta[(size_t)i];
+    om.type = d->objects[i].type;
+    om.reflection = d->objects[i].reflection;
+    std::memcpy(om.o2w, d->objects[i].object_to_world, sizeof om.o2w);
+    std::memcpy(om.w2o, d->objects[i].world_to_object, sizeof om.w2o);
+  }
+  {
+    LightState ls;
+    rc = build_lights(s.get(), d->lights, d->num_lights, false, &ls);
+    if (rc == RT_OK) adopt_lights(s.get(), &ls);
+    ls.release();
+    if (rc) return rc;
+  }
+  mark("lights");
   s->max_waves = s->num_cus * 8 * 4;  // 8 blocks of 4 waves per CU at most
   // two kernels per two-class launch: their waves' partial counters side by side
   if ((rc = s->partials.alloc((size_t)2 * s->max_waves * kStatSlots))) return rc;
@@ -1178,8 +1408,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   HIP_TRY(hipMemset(s->queue2.p, 0, s->queue2.bytes()));
   HIP_TRY(hipDeviceSynchronize());
   mark("nodes + buffers");
-  s->num_triangles = ntri;
-  s->num_nodes = nnodes;
   s->max_depth = maxdepth;
   s->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out_scene = s.release();
@@ -1246,6 +1474,42 @@ extern "C" int rt_scene_set_camera(rt_scene* s, const double c2w[16], double fov
   if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);
   if (e != hipSuccess) return fail(RT_E_DEVICE, "waiting for the scene's earlier calls: %s", hipGetErrorString(e));
   return RT_OK;
+}
+
+extern "C" int rt_scene_set_lights(rt_scene* s, const rt_light_desc* lights, int32_t num_lights) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (num_lights < 0) return fail(RT_E_INVALID, "negative light count");
+  if (num_lights > 0 && !lights) return fail(RT_E_INVALID, "null array with nonzero count");
+  for (int i = 0; i < num_lights; ++i)
+    if (lights[i].type != RT_DISTANT_LIGHT && lights[i].type != RT_POINT_LIGHT)
+      return fail(RT_E_INVALID, "light %d: bad type", i);
+  std::lock_guard<std::mutex> lk(s->mu);
+  const int prev = device_of_current();
+  if (prev != s->device) (void)hipSetDevice(s->device);
+  struct Restore {
+    int prev, dev;
+    ~Restore() {
+      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+  } restore{prev, s->device};
+  // earlier calls still read the old buffers: renders (done, the caller's
+  // stream), a pipelined call's build (bstream reads grids and sat_dev), queries
+  hipError_t e = s->done ? hipEventSynchronize(s->done) : hipSuccess;
+  if (e == hipSuccess && s->q_done_rec) e = hipEventSynchronize(s->q_done);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->bstream);
+  if (e != hipSuccess) return fail(RT_E_DEVICE, "waiting for the scene's earlier calls: %s", hipGetErrorString(e));
+  // everything into new buffers; the scene changes only when all of it succeeded
+  LightState ls;
+  const int rc = build_lights(s, lights, num_lights, true, &ls);
+  if (rc == RT_OK) {
+    adopt_lights(s, &ls);
+    s->sh64.release();  // sized by grid_ent, formed from the lights' directions: rebuilt on demand
+    s->sh64_ready = false;
+    s->orders.clear();  // the measured launch orders were the old lights'
+  }
+  ls.release();  // the old state (or the failed build's)
+  return rc;
 }
 
 namespace {
@@ -2092,11 +2356,12 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
         if (!s->sh64_ready && s->shadow_mesh >= 0) {
           if (int rc = s->sh64.alloc(s->grid_ent.n)) return rc;
           for (int li = 0; li < s->nlight && li < (int)s->grid_host.size(); ++li) {
-            const LightGridHost& lg = s->grid_host[(size_t)li];
-            if (lg.g.gu <= 0 || lg.ent.empty()) continue;
+            const LightGrid& g = s->grid_host[(size_t)li].g;  // (the header and the count survive a relight)
+            const int64_t ne = s->grid_nent[(size_t)li];
+            if (g.gu <= 0 || ne <= 0) continue;
             const int e = rtmi_build_sh64(s->f64.objects.p, s->shadow_mesh, s->f64.lights.p, li,
-                                          s->grid_ent.p + lg.g.ent_base, (int)lg.ent.size(), s->f64.tris.p,
-                                          (int32_t)s->num_nodes, s->sh64.p + lg.g.ent_base, st);
+                                          s->grid_ent.p + g.ent_base, (int)ne, s->f64.tris.p,
+                                          (int32_t)s->num_nodes, s->sh64.p + g.ent_base, st);
             if (e) return fail(RT_E_DEVICE, "shadow record build failed: %s", hipGetErrorString((hipError_t)e));
           }
           s->sh64_ready = true;
@@ -2932,7 +3197,7 @@ extern "C" int64_t rtmi_test_frame_lists(rt_scene* s, int32_t* off, int32_t* ent
 extern "C" int rtmi_test_ltri(const double* v9, const double* d, int32_t face, void* out) {
   if (!v9 || !d || !out) return fail(RT_E_INVALID, "null argument");
   const double v[3][3] = {{v9[0], v9[1], v9[2]}, {v9[3], v9[4], v9[5]}, {v9[6], v9[7], v9[8]}};
-  make_ltri(v, d, face, (LTri*)out);
+  bg::make_ltri(v, d, face, (LTri*)out);
   return RT_OK;
 }
 
@@ -3040,6 +3305,7 @@ extern "C" int64_t rtmi_test_host_lists(rt_scene* s, int32_t w, int32_t h, doubl
   const char* why = "";
   if (!build_pixel_bins(s->bin_tris, s->mesh_o2w, s->mesh_w2o, s->c2w, s->fov, w, h, &hb, &why)) return -1;
   const size_t npx = (size_t)w * (size_t)h;
+  refresh_host_lists(s);  // (after a relight the prefix sums are on the device only)
   std::vector<uint32_t> sk;
   if (!(s->skippable && build_shadow_skips(hb.off, s->skip_planes, s->mesh_w2o, s->grid_occ, s->c2w, s->fov, w, h,
                                            bias, &sk, &why)))
@@ -3052,4 +3318,66 @@ extern "C" int64_t rtmi_test_host_lists(rt_scene* s, int32_t w, int32_t h, doubl
     info[k] = std::min<uint32_t>(n, kPixCount) | (sk[k >> 2] >> (8 * (k & 3)) & 0xffu) << 24;
   }
   return total;
+}
+
+// rt_scene_set_lights' device-built arrays against the host path (the one
+// rt_scene_create takes) on the scene's faces and current lights, byte for
+// byte. out[k]: differing elements (a length difference counts each missing
+// element) of 0 the grid headers and the scene's light flags, 1 off, 2 ent
+// (padding included), 3 the occupancy prefix sums, 4 lrec, 5 grec, 6 the
+// FLight records, 7 the DevLight<double> records.
+namespace {
+template <class T>
+int64_t diff_dev(const DevBuf<T>& a, const DevBuf<T>& b) {
+  std::vector<unsigned char> ha(a.bytes()), hb(b.bytes());
+  if (a.p && !ha.empty() && hipMemcpy(ha.data(), a.p, ha.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (b.p && !hb.empty() && hipMemcpy(hb.data(), b.p, hb.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const size_t n = std::min(a.n, b.n);
+  int64_t bad = (int64_t)(std::max(a.n, b.n) - n);
+  for (size_t k = 0; k < n; ++k) bad += std::memcmp(&ha[k * sizeof(T)], &hb[k * sizeof(T)], sizeof(T)) != 0 ? 1 : 0;
+  return bad;
+}
+}  // namespace
+
+extern "C" int rtmi_test_relight_diff(rt_scene* s, int64_t out[8]) {
+  if (!s || !out) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  const int prev = device_of_current();
+  if (prev != s->device) (void)hipSetDevice(s->device);
+  HIP_TRY(hipDeviceSynchronize());
+  LightState h;
+  int rc = build_lights(s, s->light_desc.data(), s->nlight, false, &h);
+  if (rc == RT_OK) {
+    out[0] = diff_dev(s->grids, h.grids);
+    out[0] += (s->has_grids != h.has_grids) + (s->lrec_mask != h.lrec_mask) + (s->skippable != h.skippable) +
+              (s->lean64_plane != h.lean64_plane) + (s->has_point_light != h.has_point_light) +
+              (std::memcmp(s->sat_off, h.sat_off, sizeof h.sat_off) != 0) + (s->lrec_ntri != h.lrec_ntri) +
+              (s->has_obj_grids != h.has_obj_grids) + (s->grid_nent != h.grid_nent);
+    for (size_t li = 0; li < h.grid_occ.size() && li < s->grid_occ.size(); ++li)
+      out[0] += std::memcmp(&s->grid_occ[li].g, &h.grid_occ[li].g, sizeof(LightGrid)) != 0;
+    out[1] = diff_dev(s->grid_off, h.grid_off);
+    out[2] = diff_dev(s->grid_ent, h.grid_ent);
+    out[3] = diff_dev(s->sat_dev, h.sat_dev);
+    out[4] = diff_dev(s->lrec, h.lrec);
+    out[5] = diff_dev(s->grec, h.grec);
+    out[6] = diff_dev(s->f32.lights, h.f32_lights);
+    out[7] = diff_dev(s->f64.lights, h.f64_lights);
+    for (int k = 0; k < 8; ++k)
+      if (out[k] < 0) rc = fail(RT_E_DEVICE, "reading the light arrays back failed");
+  }
+  h.release();
+  if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);
+  return rc;
+}
+
+// enable: time the device builder's passes from the next relight on (events
+// between them). ms (may be null): the passes of the last relight, summed
+// over its lights (faces, count, scan, records, fill + order, prefix sums);
+// zeros when it was not timed (tools/relight_bench.py).
+extern "C" int rtmi_test_relight_passes(rt_scene* s, int32_t enable, float ms[6]) {
+  if (!s) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (ms) std::copy(s->relight_ms, s->relight_ms + 6, ms);
+  s->relight_timed = enable != 0;
+  return RT_OK;
 }

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import abi, glm
 from ._lib import RtmiError, check, lib
-from .scene import Options, Scene, Stats, flatten
+from .scene import Options, Scene, Stats, flatten, flatten_lights
 
 
 def initRenderer(device=0):
@@ -68,6 +68,14 @@ class DeviceScene:
         f = self.scene.fov if fov is None else fov
         arr = (C.c_double * 16)(*[float(x) for x in glm.flat(m)])
         check(lib().rt_scene_set_camera(self.h, arr, float(f)))
+
+    def set_lights(self, lights=None):
+        """Scene.lights for the next calls (rt_scene_set_lights): any number
+        and mix of DistantLight / PointLight; None: this DeviceScene's
+        Scene's current lights. The geometry, BVH and camera stay; the
+        scene then renders exactly as one created with these lights."""
+        ls = list(self.scene.lights if lights is None else lights)
+        check(lib().rt_scene_set_lights(self.h, flatten_lights(ls), len(ls)))
 
     # -- host framebuffer (the pool-compatible path) ----------------------
     def render_lines(self, opts: Options, fb, y0, y1, step=1, maxStep=1) -> Stats:
@@ -266,12 +274,13 @@ def unshard_bands_device(d_gathered, d_fb, width, height, band_h, world, stream=
 
 
 def _shape_key(scene: Scene):
-    """Everything of a Scene except the camera that the device copy holds:
-    object transforms, materials, sphere radii, the FULL box bounds (all of
-    vmin / vmax, geom.nim:169-170), mesh sizes, lights, background — the
-    fingerprint INTEGRATION.md's Nim binding (shapeHash) keeps. Mesh vertices
-    edited in place (same sizes) are not hashed per call: invalidateScene."""
-    from .scene import Box, DistantLight, Sphere, TriangleMesh
+    """Everything of a Scene except the camera and the lights that the device
+    copy holds: object transforms, materials, sphere radii, the FULL box
+    bounds (all of vmin / vmax, geom.nim:169-170), mesh sizes, background —
+    the fingerprint INTEGRATION.md's Nim binding (shapeHash) keeps; a change
+    rebuilds the device scene. Mesh vertices edited in place (same sizes) are
+    not hashed per call: invalidateScene."""
+    from .scene import Box, Sphere, TriangleMesh
     parts = []
     for o in scene.objects:
         g = o.geometry
@@ -284,10 +293,18 @@ def _shape_key(scene: Scene):
             parts += [g.vmin.tobytes(), g.vmax.tobytes()]
         elif isinstance(g, TriangleMesh):
             parts += [g.vertices.shape[0], g.faces.shape[0], id(g.vertices), id(g.faces)]
+    parts.append(np.asarray(scene.bgColor, np.float64).tobytes())
+    return tuple(parts)
+
+
+def _lights_key(scene: Scene):
+    """The lights' fingerprint (the Nim binding's lightsHash): a change is
+    pushed to the existing device copy (rt_scene_set_lights)."""
+    from .scene import DistantLight
+    parts = []
     for li in scene.lights:
         parts += [type(li).__name__, np.asarray(li.color, np.float64).tobytes(), float(li.intensity),
                   np.asarray(li.dir if isinstance(li, DistantLight) else li.pos, np.float64).tobytes()]
-    parts.append(np.asarray(scene.bgColor, np.float64).tobytes())
     return tuple(parts)
 
 
@@ -296,10 +313,10 @@ class _Entry:
     the renderLine calls running on it (renders happen outside the cache's
     lock, so a replaced or invalidated copy is closed by whichever comes
     last: the replacement, or the last of those calls)."""
-    __slots__ = ("ds", "shape", "cam", "fov", "users", "retired")
+    __slots__ = ("ds", "shape", "lights", "cam", "fov", "users", "retired")
 
-    def __init__(self, ds, shape, cam, fov):
-        self.ds, self.shape, self.cam, self.fov = ds, shape, cam, fov
+    def __init__(self, ds, shape, lights, cam, fov):
+        self.ds, self.shape, self.lights, self.cam, self.fov = ds, shape, lights, cam, fov
         self.users = 0
         self.retired = False
 
@@ -307,7 +324,8 @@ class _Entry:
 class _DeviceCache:
     """The Nim binding's `deviceScene` in Python: one device
     copy per Scene, created on first use, re-created when the shape key
-    changes, its camera pushed (rt_scene_set_camera) when Scene.cameraToWorld
+    changes, its lights pushed (rt_scene_set_lights) when only Scene.lights
+    changed, its camera pushed (rt_scene_set_camera) when Scene.cameraToWorld
     / fov moved — renderLine re-reads them on every call (renderer.nim:135-136,
     150-153). Re-entrant like renderLine (the pool calls it from
     countProcessors() threads at once, workerpool.nim:72-99): lookups,
@@ -335,6 +353,7 @@ class _DeviceCache:
         entry to release() when the call has returned."""
         import weakref
         shape = _shape_key(scene)
+        lights = _lights_key(scene)
         cam = np.asarray(scene.cameraToWorld, np.float64).tobytes()
         fov = float(scene.fov)
         stale = None
@@ -342,17 +361,21 @@ class _DeviceCache:
             key = id(scene)
             item = self._entries.get(key)
             e = item[1] if item is not None and item[0]() is scene else None
-            if e is not None and e.shape != shape:  # geometry / materials / lights changed
+            if e is not None and e.shape != shape:  # geometry / materials changed
                 stale = self._drop(e)
                 e = None
             if e is None:
                 ds = DeviceScene(scene, device)
                 ds.scene = weakref.proxy(scene)  # the cache must not keep the Scene alive
-                e = _Entry(ds, shape, cam, fov)
+                e = _Entry(ds, shape, lights, cam, fov)
                 self._entries[key] = (weakref.ref(scene, lambda _r, k=key: self._collected(k)), e)
-            elif e.cam != cam or e.fov != fov:  # the camera moved: the next call renders it
-                e.ds.set_camera(scene.cameraToWorld, fov)
-                e.cam, e.fov = cam, fov
+            else:
+                if e.lights != lights:  # only the lights changed: the copy is relit, not rebuilt
+                    e.ds.set_lights(scene.lights)
+                    e.lights = lights
+                if e.cam != cam or e.fov != fov:  # the camera moved: the next call renders it
+                    e.ds.set_camera(scene.cameraToWorld, fov)
+                    e.cam, e.fov = cam, fov
             e.users += 1
         if stale is not None:
             stale.close()
@@ -485,6 +508,11 @@ class MultiDeviceScene:
         """rt_scene_set_camera on every rank's scene."""
         arr = (C.c_double * 16)(*[float(x) for x in glm.flat(cameraToWorld)])
         check(lib().rt_multi_set_camera(self.h, arr, float(fov)))
+
+    def set_lights(self, lights):
+        """rt_scene_set_lights on every rank's scene."""
+        ls = list(lights)
+        check(lib().rt_multi_set_lights(self.h, flatten_lights(ls), len(ls)))
 
     def render_frame(self, opts: Options, fb) -> Stats:
         """Whole frame into a host (h, w, 3) float32 array."""

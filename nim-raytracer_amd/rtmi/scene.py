@@ -203,6 +203,25 @@ def _d(arr, n):
     return a
 
 
+def flatten_lights(lights):
+    """The rt_light_desc array of a list of lights (at least one element, so
+    the pointer is never null): rt_scene_create's and rt_scene_set_lights'."""
+    out = (abi.rt_light_desc * max(1, len(lights)))()
+    for i, l in enumerate(lights):
+        d = out[i]
+        d.color = _d(l.color, 3)
+        d.intensity = float(l.intensity)
+        if isinstance(l, DistantLight):
+            d.type = abi.RT_DISTANT_LIGHT
+            d.dir = _d(l.dir, 3)
+        elif isinstance(l, PointLight):
+            d.type = abi.RT_POINT_LIGHT
+            d.pos = _d(l.pos, 3)
+        else:
+            raise TypeError(f"unsupported light {type(l).__name__}")
+    return out
+
+
 class FlatScene:
     """rt_scene_desc plus the buffers it points into (kept alive together)."""
 
@@ -245,19 +264,7 @@ class FlatScene:
             m.num_faces = g.faces.shape[0]
             m.normals = (None if g.normals is None else
                          g.normals.ctypes.data_as(C.POINTER(C.c_double)))
-        self._lights = (abi.rt_light_desc * max(1, len(scene.lights)))()
-        for i, l in enumerate(scene.lights):
-            d = self._lights[i]
-            d.color = _d(l.color, 3)
-            d.intensity = float(l.intensity)
-            if isinstance(l, DistantLight):
-                d.type = abi.RT_DISTANT_LIGHT
-                d.dir = _d(l.dir, 3)
-            elif isinstance(l, PointLight):
-                d.type = abi.RT_POINT_LIGHT
-                d.pos = _d(l.pos, 3)
-            else:
-                raise TypeError(f"unsupported light {type(l).__name__}")
+        self._lights = flatten_lights(scene.lights)
         desc = abi.rt_scene_desc()
         desc.objects = C.cast(self._objs, C.POINTER(abi.rt_object_desc))
         desc.num_objects = len(objs)
