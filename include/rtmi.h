@@ -329,6 +329,35 @@ int rt_scene_set_camera(rt_scene *scene, const double camera_to_world[16],
 int rt_scene_set_lights(rt_scene *scene, const rt_light_desc *lights,
                         int32_t num_lights);
 
+/* Replace the vertex positions of mesh `mesh` (index into the rt_scene_desc.meshes
+ * the scene was created from). The face index array, the vertex count and the
+ * face count stay: num_vertices must equal the count given at create. normals:
+ * num_faces*3 face normals, or NULL = recompute as rt_scene_create does for
+ * rt_mesh_desc.normals == NULL (calcNormals).
+ * From the next call on the scene answers exactly as one created by
+ * rt_scene_create from the same description with these vertices: frames in
+ * both precisions, Stats, the rt_trace_rays / rt_pick_pixels answers (t, obj,
+ * face, normals), rt_scene_last_split and rt_scene_last_lean_kernel are the
+ * same, bit for bit. The tree keeps the topology and leaf order it was built
+ * with; only its boxes are refitted (on the device), so traversal may be
+ * slower than on a fresh tree after a large deformation, never different.
+ * Waits for everything in flight on the scene (renders, pipelined builds,
+ * queries). Camera, lights, objects, materials, buffer sets and the other
+ * meshes are kept; the light grids are rebuilt over the new faces.
+ * RT_E_INVALID for a null scene or vertex array, a mesh index out of range,
+ * a num_vertices different from the mesh's, or a non-finite vertex that a
+ * face references. On any failure the scene keeps its previous geometry.
+ * A mesh of 0 faces is RT_OK and launches nothing. */
+int rt_scene_set_mesh_vertices(rt_scene *scene, int32_t mesh, const double *vertices,
+                               int64_t num_vertices, const double *normals);
+/* The same with the arrays in device memory (a deformation computed on the GPU:
+ * nothing crosses PCIe). The arrays are read after the work already enqueued on
+ * hip_stream; the call returns when the scene is updated and the buffers may be
+ * reused. */
+int rt_scene_set_mesh_vertices_device(rt_scene *scene, int32_t mesh, const double *d_vertices,
+                                      int64_t num_vertices, const double *d_normals,
+                                      void *hip_stream);
+
 /* ---- rendering ----------------------------------------------------------
  * All render calls implement renderLine (renderer.nim:162-211) for every row
  * y in countup(y0, y1 - 1, step):
@@ -415,6 +444,9 @@ int rt_multi_set_camera(rt_multi *m, const double camera_to_world[16],
 /* rt_scene_set_lights on every rank's scene. */
 int rt_multi_set_lights(rt_multi *m, const rt_light_desc *lights,
                         int32_t num_lights);
+/* rt_scene_set_mesh_vertices on every rank's scene. */
+int rt_multi_set_mesh_vertices(rt_multi *m, int32_t mesh, const double *vertices,
+                               int64_t num_vertices, const double *normals);
 int rt_multi_destroy(rt_multi *m);
 
 /* ---- render queue (workerpool.nim WorkerPool[WorkMsg, ResponseMsg]) ---- */

@@ -271,6 +271,73 @@ bool build_bvh(const double* v, const int32_t* f, int64_t nf, const BvhBuildPara
   return validate_bvh(*out, nf, err);
 }
 
+bool bvh_margin(const double* v, const int32_t* f, int64_t nf, double* inflate) {
+  double mag = 0.0;
+  Box all;
+  all.reset();
+  for (int64_t i = 0; i < nf; ++i)
+    for (int k = 0; k < 3; ++k) {
+      const double* p = &v[3 * (size_t)f[3 * i + k]];
+      for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(p[a])) return false;
+      all.grow(p);
+    }
+  double extent = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    extent = std::max(extent, all.hi[a] - all.lo[a]);
+    mag = std::max(mag, std::max(std::fabs(all.lo[a]), std::fabs(all.hi[a])));
+  }
+  if (!std::isfinite(mag) || !std::isfinite(extent)) return false;
+  *inflate = std::ldexp(std::max(extent, mag), -20) + 1e-30;  // = build_bvh
+  return true;
+}
+
+bool refit_bvh(const double* v, const int32_t* f, int64_t nf, BvhResult* r, const char** err) {
+  if (nf <= 0 || r->nodes.empty()) return true;
+  BvhBuildParams prm;
+  std::vector<int32_t> no_order;
+  std::vector<BvhNode> no_nodes;
+  Builder B(prm, no_order, no_nodes);  // lo32 / hi32 with the new margin
+  if (!bvh_margin(v, f, nf, &B.inflate)) {
+    *err = "mesh has non-finite vertices";
+    return false;
+  }
+  // parents before children (any layout): depth-first from the root, then backwards
+  std::vector<int32_t> pre;
+  pre.reserve(r->nodes.size());
+  pre.push_back(0);
+  for (size_t k = 0; k < pre.size(); ++k) {
+    const BvhNode& nd = r->nodes[(size_t)pre[k]];
+    if (nd.n0 == 0 && nd.c0 > 0) pre.push_back(nd.c0);
+    if (nd.n1 == 0 && nd.c1 > 0) pre.push_back(nd.c1);
+  }
+  for (size_t k = pre.size(); k-- > 0;) {
+    BvhNode& nd = r->nodes[(size_t)pre[k]];
+    for (int slot = 0; slot < 2; ++slot) {
+      const int32_t c = slot == 0 ? nd.c0 : nd.c1, n = slot == 0 ? nd.n0 : nd.n1;
+      float* lo = slot == 0 ? nd.lo0 : nd.lo1;
+      float* hi = slot == 0 ? nd.hi0 : nd.hi1;
+      if (n > 0) {
+        Box bb;
+        bb.reset();
+        for (int32_t j = c; j < c + n; ++j)
+          for (int q = 0; q < 3; ++q) bb.grow(&v[3 * (size_t)f[3 * (size_t)r->order[(size_t)j] + q]]);
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = B.lo32(bb.lo[a]);
+          hi[a] = B.hi32(bb.hi[a]);
+        }
+      } else if (c > 0) {
+        const BvhNode& ch = r->nodes[(size_t)c];
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = std::min(ch.lo0[a], ch.lo1[a]);
+          hi[a] = std::max(ch.hi0[a], ch.hi1[a]);
+        }
+      }
+    }
+  }
+  return true;
+}
+
 bool validate_bvh(const BvhResult& r, int64_t nf, const char** err) {
   const int32_t nn = (int32_t)r.nodes.size();
   if (nf > 0 && nn == 0) {

@@ -46,6 +46,19 @@ bool build_bvh_device(const double* d_vertices, const int32_t* d_faces, int64_t 
 bool pack_triangles_device(const double* d_vertices, const int32_t* d_faces, const int32_t* d_order, int64_t nf,
                            TriFast* d_fast, TriF64* d_f64, void* stream);
 
+// Host refit: the boxes of r->nodes formed again for new vertex positions,
+// topology and leaf order kept. A leaf child's box is its faces' float64
+// bounds inflated by the builders' margin (of the new positions) and rounded
+// outward, an inner child's the union of that node's two boxes: outward
+// rounding is monotone, so these are the boxes either builder would store for
+// this topology. The reference the device refit (rt_mesh_gpu.hip) is compared
+// with. False (r untouched) when a face references a non-finite vertex.
+bool refit_bvh(const double* vertices, const int32_t* faces, int64_t nf, BvhResult* r, const char** err);
+
+// The builders' margin for these positions (2^-20 of the mesh scale); false
+// when a face references a non-finite vertex.
+bool bvh_margin(const double* vertices, const int32_t* faces, int64_t nf, double* inflate);
+
 // Structure check shared by both builders: every child reference in range,
 // no inner node points at the root, leaves cover every face exactly once.
 bool validate_bvh(const BvhResult& r, int64_t nf, const char** err);

@@ -243,6 +243,18 @@ int rt_multi_set_lights(rt_multi* m, const rt_light_desc* lights, int32_t num_li
   return RT_OK;
 }
 
+int rt_multi_set_mesh_vertices(rt_multi* m, int32_t mesh, const double* vertices, int64_t num_vertices,
+                               const double* normals) {
+  if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  CurrentDevice keep;
+  for (rt_scene* s : m->scene) {
+    const int rc = rt_scene_set_mesh_vertices(s, mesh, vertices, num_vertices, normals);
+    if (rc) return rc;
+  }
+  return RT_OK;
+}
+
 int rt_multi_destroy(rt_multi* m) {
   if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
   {

@@ -29,6 +29,7 @@
 #include "rt_common.h"
 #include "rt_frame.h"
 #include "rt_lights_gpu.h"
+#include "rt_mesh_gpu.h"
 #include "rt_query.h"
 
 using namespace rtmi;
@@ -266,13 +267,43 @@ struct rt_scene {
   // stale until a test hook asks for them (refresh_host_lists).
   std::vector<rt_light_desc> light_desc;
   struct ObjMeta {
-    int32_t type;
+    int32_t type, mesh;
     double reflection, o2w[16], w2o[16];
   };
   std::vector<ObjMeta> obj_meta;
   std::vector<int64_t> grid_nent;
   bool mirrors_stale = false;
   double bin_scale = 0.0;          // the grids' length scale of bin_dev (0: not yet reduced)
+  // rt_scene_set_mesh_vertices: what an update reads of every mesh (its
+  // current vertices, its faces, its leaf order, where its records and nodes
+  // lie), the tree's parent table (2 * parent + slot, -1: a root) with the
+  // refit's arrival counters, and host copies of the records that hold a
+  // mesh's box. bin_tris' vertices are stale after an update until a hook
+  // asks for them (refresh_bin_tris). h_nodes: the nodes as created (the
+  // child references; the hooks' host refit starts from them).
+  struct MeshKeep {
+    DevBuf<double> verts;
+    DevBuf<int32_t> faces, order;
+    int64_t nv = 0, nf = 0, tri_base = 0;
+    int32_t node_base = 0, node_count = 0;
+    bool normals_given = false;
+  };
+  std::vector<MeshKeep> mesh_keep;
+  DevBuf<int32_t> refit_parent, refit_arrivals;
+  DevBuf<unsigned long long> mesh_scratch;
+  std::vector<BvhNode> h_nodes;
+  std::vector<DevMesh<float>> h_dm32;
+  std::vector<DevMesh<double>> h_dm64;
+  std::vector<FMesh> h_fm;
+  std::vector<FObj> h_fo;
+  bool bin_tris_stale = false;
+  bool mesh_timed = false;         // time the update's passes (rtmi_test_mesh_update_passes)
+  float mesh_ms[6] = {};           // the last timed update's passes
+  size_t mesh_keep_bytes() const {
+    size_t b = refit_parent.bytes() + refit_arrivals.bytes() + mesh_scratch.bytes();
+    for (const MeshKeep& k : mesh_keep) b += k.verts.bytes() + k.faces.bytes() + k.order.bytes();
+    return b;
+  }
   bool relight_timed = false;      // time the device builder's passes (rtmi_test_relight_passes)
   float relight_ms[6] = {};        // the last timed relight's passes
   // camera-dependent data of the float32 kernels (rt_frame.h): rebuilt on
@@ -365,6 +396,14 @@ struct rt_scene {
     bin_dev.release();
     sat_dev.release();
     objbox_dev.release();
+    for (MeshKeep& k : mesh_keep) {
+      k.verts.release();
+      k.faces.release();
+      k.order.release();
+    }
+    refit_parent.release();
+    refit_arrivals.release();
+    mesh_scratch.release();
     if (fork) (void)hipEventDestroy(fork);
     for (hipEvent_t& e : tev)
       if (e) (void)hipEventDestroy(e);
@@ -730,9 +769,19 @@ struct LightState {
   }
 };
 
+// bin_tris' vertices after a mesh update, for the host builders and the
+// hooks that read them: bin_dev holds the same records.
+int refresh_bin_tris(rt_scene* s) {
+  if (!s->bin_tris_stale) return RT_OK;
+  HIP_TRY(hipMemcpy(s->bin_tris.data(), s->bin_dev.p, s->bin_tris.size() * sizeof(BinTri), hipMemcpyDeviceToHost));
+  s->bin_tris_stale = false;
+  return RT_OK;
+}
+
 // The distant lights' mesh grids, records and prefix sums by the host
 // builders (rt_bins.cpp): rt_scene_create's path.
 int mesh_grids_host(rt_scene* s, const rt_light_desc* lights, int32_t nl, LightState* L, bool* any_out) {
+  if (int rrc = refresh_bin_tris(s)) return rrc;
   const int64_t nnodes = s->num_nodes, ntri = s->num_triangles;
   int rc;
   std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
@@ -1020,6 +1069,7 @@ void adopt_lights(rt_scene* s, LightState* L) {
 // forms what the device built (rtmi_test_relight_diff checks that it does).
 void refresh_host_lists(rt_scene* s) {
   if (!s->mirrors_stale) return;
+  (void)refresh_bin_tris(s);
   for (size_t li = 0; li < s->grid_occ.size(); ++li) {
     const LightGrid kept = s->grid_occ[li].g;
     if (kept.gu <= 0) continue;
@@ -1033,6 +1083,44 @@ void refresh_host_lists(rt_scene* s) {
     s->grid_occ[li].lists = &s->grid_host[li];
   }
   s->mirrors_stale = false;
+}
+
+// An object's bin box (rt_bins.h ObjBox): the world box of its object-space
+// box lo..hi, through the inverse of the world_to_object the kernel
+// transforms rays with. rt_scene_create and a mesh update form the same.
+void world_obj_box(int32_t type, const double* w2o, const double lo[3], const double hi[3], ObjBox* out) {
+  ObjBox& b = *out;
+  double o2w[16];
+  b.always = type == RT_PLANE || rt_mat4_inverse(w2o, o2w) != RT_OK;
+  if (b.always) return;
+  for (int k = 0; k < 3; ++k) {
+    b.lo[k] = INFINITY;
+    b.hi[k] = -INFINITY;
+  }
+  for (int c = 0; c < 8; ++c) {
+    const double q[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
+    for (int r = 0; r < 3; ++r) {
+      const double w = o2w[0 * 4 + r] * q[0] + o2w[1 * 4 + r] * q[1] + o2w[2 * 4 + r] * q[2] + o2w[3 * 4 + r];
+      b.corner[c][r] = w;
+      b.lo[r] = std::min(b.lo[r], w);
+      b.hi[r] = std::max(b.hi[r], w);
+    }
+  }
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(b.lo[k]) || !std::isfinite(b.hi[k])) b.always = true;
+}
+
+void dev_obj_boxes(const std::vector<ObjBox>& boxes, std::vector<DevObjBox>& ob) {
+  ob.assign(boxes.size(), DevObjBox{});
+  for (size_t i = 0; i < boxes.size(); ++i) {
+    const ObjBox& b = boxes[i];
+    for (int k = 0; k < 3; ++k) {
+      ob[i].lo[k] = b.lo[k];
+      ob[i].hi[k] = b.hi[k];
+    }
+    ob[i].always = b.always ? 1 : 0;
+    ob[i].pad = 0;
+  }
 }
 
 }  // namespace
@@ -1247,6 +1335,9 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<FLight> fl;
     fill_fast_records(d, m, fo, fx, fm, fl);
     for (const FObj& q : fo) s->h_obj_ty.push_back(q.t[1]);
+    s->h_dm32 = m;
+    s->h_fm = fm;
+    s->h_fo = fo;
     int rc;
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
         (rc = s->f32.normals.upload(n)))
@@ -1260,6 +1351,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<double> n;
     fill_precision<double>(d, normals, bvhs, node_base, aabbs, o, l, m, nullptr, n);
     mark("fp64 records");
+    s->h_dm64 = m;
     int rc;
     if ((rc = s->f64.objects.upload(o)) || (rc = s->f64.meshes.upload(m)) ||
         (rc = s->f64.normals.upload(n)))
@@ -1281,17 +1373,39 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     }
     HIP_TRY(hipMemcpy(s->f64.tris.p + ntri, pad.data(), pad.size() * sizeof(TriF64), hipMemcpyHostToDevice));
     int64_t base = 0;
+    s->mesh_keep.resize((size_t)d->num_meshes);
     for (int m = 0; m < d->num_meshes; ++m) {
       const int64_t nf = d->meshes[m].num_faces;
-      DevBuf<int32_t> order;
+      // the leaf order stays on the device: a mesh update packs with it again
+      rt_scene::MeshKeep& keep = s->mesh_keep[(size_t)m];
+      DevBuf<int32_t>& order = keep.order;
       if ((rc = order.upload(bvhs[(size_t)m].order))) return rc;
       const bool ok = pack_triangles_device(d_verts[(size_t)m].p, d_faces[(size_t)m].p, order.p, nf,
                                             f32_tris + base, s->f64.tris.p + base, s->stream);
       HIP_TRY(hipStreamSynchronize(s->stream));
-      order.release();
       if (!ok) return fail(RT_E_DEVICE, "mesh %d: triangle packing failed", m);
+      keep.nv = d->meshes[m].num_vertices;
+      keep.nf = nf;
+      keep.tri_base = base;
+      keep.node_base = node_base[(size_t)m];
+      keep.node_count = (int32_t)bvhs[(size_t)m].nodes.size();
+      keep.normals_given = d->meshes[m].normals != nullptr;
       base += nf;
     }
+  }
+  {
+    // the refit's parent table: every inner child names its node and slot
+    std::vector<int32_t> parent(all_nodes.size(), -1);
+    for (size_t i = 0; i < all_nodes.size(); ++i) {
+      const BvhNode& nd = all_nodes[i];
+      if (nd.n0 == 0 && nd.c0 >= 0) parent[(size_t)nd.c0] = (int32_t)(2 * i);
+      if (nd.n1 == 0 && nd.c1 >= 0) parent[(size_t)nd.c1] = (int32_t)(2 * i + 1);
+    }
+    int rc;
+    if ((rc = s->refit_parent.upload(parent)) || (rc = s->refit_arrivals.alloc(all_nodes.size())) ||
+        (rc = s->mesh_scratch.alloc((size_t)kMeshBoundsWords)))
+      return rc;
+    s->h_nodes = all_nodes;
   }
   mark("triangle packing");
   int rc = s->nodes.upload(all_nodes);
@@ -1343,40 +1457,16 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     for (int i = 0; i < d->num_objects; ++i) {
       const rt_object_desc& ob = d->objects[i];
       ObjBox& b = s->obj_boxes[(size_t)i];
-      double lo[3], hi[3], o2w[16];
-      b.always = ob.type == RT_PLANE || rt_mat4_inverse(ob.world_to_object, o2w) != RT_OK;
-      if (b.always) continue;
-      for (int k = 0; k < 3; ++k) {
+      double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+      for (int k = 0; k < 3 && ob.type != RT_PLANE; ++k) {
         lo[k] = ob.type == RT_SPHERE ? -std::fabs(ob.radius) : ob.type == RT_BOX ? ob.box_min[k] : aabbs[(size_t)ob.mesh][k];
         hi[k] = ob.type == RT_SPHERE ? std::fabs(ob.radius) : ob.type == RT_BOX ? ob.box_max[k] : aabbs[(size_t)ob.mesh][3 + k];
-        b.lo[k] = INFINITY;
-        b.hi[k] = -INFINITY;
       }
-      // the world box of the object box, through the inverse of the
-      // world_to_object the kernel transforms rays with
-      for (int c = 0; c < 8; ++c) {
-        const double q[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
-        for (int r = 0; r < 3; ++r) {
-          const double w = o2w[0 * 4 + r] * q[0] + o2w[1 * 4 + r] * q[1] + o2w[2 * 4 + r] * q[2] + o2w[3 * 4 + r];
-          b.corner[c][r] = w;
-          b.lo[r] = std::min(b.lo[r], w);
-          b.hi[r] = std::max(b.hi[r], w);
-        }
-      }
-      for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(b.lo[k]) || !std::isfinite(b.hi[k])) b.always = true;
+      world_obj_box(ob.type, ob.world_to_object, lo, hi, &b);
     }
     s->objbins = true;
-    std::vector<DevObjBox> ob((size_t)d->num_objects);
-    for (int i = 0; i < d->num_objects; ++i) {
-      const ObjBox& b = s->obj_boxes[(size_t)i];
-      for (int k = 0; k < 3; ++k) {
-        ob[(size_t)i].lo[k] = b.lo[k];
-        ob[(size_t)i].hi[k] = b.hi[k];
-      }
-      ob[(size_t)i].always = b.always ? 1 : 0;
-      ob[(size_t)i].pad = 0;
-    }
+    std::vector<DevObjBox> ob;
+    dev_obj_boxes(s->obj_boxes, ob);
     if ((rc = s->objbox_dev.upload(ob))) return rc;
     mark("object bins");
   }
@@ -1387,6 +1477,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   for (int i = 0; i < d->num_objects; ++i) {
     rt_scene::ObjMeta& om = s->obj_meta[(size_t)i];
     om.type = d->objects[i].type;
+    om.mesh = d->objects[i].type == RT_MESH ? d->objects[i].mesh : -1;
     om.reflection = d->objects[i].reflection;
     std::memcpy(om.o2w, d->objects[i].object_to_world, sizeof om.o2w);
     std::memcpy(om.w2o, d->objects[i].world_to_object, sizeof om.w2o);
@@ -1409,7 +1500,11 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   HIP_TRY(hipDeviceSynchronize());
   mark("nodes + buffers");
   s->max_depth = maxdepth;
-  s->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (int m = 0; m < d->num_meshes; ++m) {  // the scene keeps the meshes' device arrays (mesh updates)
+    std::swap(s->mesh_keep[(size_t)m].verts, d_verts[(size_t)m]);
+    std::swap(s->mesh_keep[(size_t)m].faces, d_faces[(size_t)m]);
+  }
+  s->build_ms =std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out_scene = s.release();
   return RT_OK;
 }
@@ -1453,7 +1548,8 @@ extern "C" int rt_scene_get_info(const rt_scene* s, rt_scene_info* out) {
                                 s->grid_ent.bytes() + s->obj_grids.bytes() + s->obj_grid_mask.bytes() +
                                 s->bin_dev.bytes() + s->sat_dev.bytes() + s->objbox_dev.bytes() +
                                 s->lrec.bytes() + s->grec.bytes() + s->fr.bytes() + s->fr2.bytes() +
-                                s->q_partials.bytes() + s->q_sort.bytes() + s->q_stage.bytes());
+                                s->q_partials.bytes() + s->q_sort.bytes() + s->q_stage.bytes() +
+                                s->mesh_keep_bytes());
   out->build_ms = s->build_ms;
   return RT_OK;
 }
@@ -1510,6 +1606,236 @@ extern "C" int rt_scene_set_lights(rt_scene* s, const rt_light_desc* lights, int
   }
   ls.release();  // the old state (or the failed build's)
   return rc;
+}
+
+namespace {
+
+// Everything a mesh update builds before the scene changes; after the
+// hand-over it holds the scene's previous buffers. Released on every path.
+struct MeshState {
+  DevBuf<double> verts, given;
+  DevBuf<BvhNode> tree, nodes;
+  DevBuf<TriF64> tris;
+  DevBuf<float> n32;
+  DevBuf<double> n64;
+  DevBuf<DevBinTri> bin;
+  DevBuf<DevMesh<double>> dm64;
+  DevBuf<FMesh> fm;
+  DevBuf<FObj> fo;
+  DevBuf<DevObjBox> objbox;
+  ~MeshState() {
+    verts.release(); given.release(); tree.release(); nodes.release(); tris.release(); n32.release();
+    n64.release(); bin.release(); dm64.release(); fm.release(); fo.release(); objbox.release();
+  }
+};
+
+template <class T>
+int copy_dev(DevBuf<T>& dst, const DevBuf<T>& src, hipStream_t st) {
+  if (int rc = dst.alloc(src.n)) return rc;
+  if (src.p && src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, st));
+  return RT_OK;
+}
+
+// rt_scene_set_mesh_vertices*: `vertices` / `normals` are host arrays
+// (device == false) or device arrays read behind `caller`.
+int set_mesh_vertices(rt_scene* s, int32_t mesh, const double* vertices, int64_t num_vertices, const double* normals,
+                      bool device, hipStream_t caller) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!vertices) return fail(RT_E_INVALID, "null vertex array");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (mesh < 0 || mesh >= s->nmesh) return fail(RT_E_INVALID, "mesh index %d out of range (%d meshes)", mesh, s->nmesh);
+  rt_scene::MeshKeep& keep = s->mesh_keep[(size_t)mesh];
+  if (num_vertices != keep.nv)
+    return fail(RT_E_INVALID, "mesh %d has %lld vertices, not %lld: a mesh update keeps the counts", mesh,
+                (long long)keep.nv, (long long)num_vertices);
+  const int prev = device_of_current();
+  if (prev != s->device) (void)hipSetDevice(s->device);
+  struct Restore {
+    int prev, dev;
+    ~Restore() {
+      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+  } restore{prev, s->device};
+  // earlier calls still read the old buffers (rt_scene_set_lights)
+  hipError_t e = s->done ? hipEventSynchronize(s->done) : hipSuccess;
+  if (e == hipSuccess && s->q_done_rec) e = hipEventSynchronize(s->q_done);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->bstream);
+  if (e != hipSuccess) return fail(RT_E_DEVICE, "waiting for the scene's earlier calls: %s", hipGetErrorString(e));
+  const int64_t nf = keep.nf, nv = keep.nv;
+  if (nf == 0) return RT_OK;
+  const auto hip_fail = [](int err) {
+    return fail(err == (int)hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_DEVICE, "mesh update: %s",
+                hipGetErrorString((hipError_t)err));
+  };
+  const bool timed = s->mesh_timed;
+  float ms[6] = {};
+  auto tp = std::chrono::steady_clock::now();
+  const auto lap = [&](int k) {  // timed runs wait after every pass
+    if (!timed) return;
+    (void)hipStreamSynchronize(s->stream);
+    const auto now = std::chrono::steady_clock::now();
+    ms[k] += std::chrono::duration<float, std::milli>(now - tp).count();
+    tp = now;
+  };
+  hipStream_t st = s->stream;
+  int rc;
+  MeshState ns;
+  // the scene's own copy of the arrays: the caller's may be reused on return
+  if ((rc = ns.verts.alloc((size_t)nv * 3))) return rc;
+  if (normals && (rc = ns.given.alloc((size_t)nf * 3))) return rc;
+  if (device) {
+    HIP_TRY(hipMemcpyAsync(ns.verts.p, vertices, (size_t)nv * 3 * sizeof(double), hipMemcpyDeviceToDevice, caller));
+    if (normals)
+      HIP_TRY(hipMemcpyAsync(ns.given.p, normals, (size_t)nf * 3 * sizeof(double), hipMemcpyDeviceToDevice, caller));
+    HIP_TRY(hipStreamSynchronize(caller));
+  } else {
+    HIP_TRY(hipMemcpy(ns.verts.p, vertices, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (normals) HIP_TRY(hipMemcpy(ns.given.p, normals, (size_t)nf * 3 * sizeof(double), hipMemcpyHostToDevice));
+  }
+  lap(0);
+  // 1. bounds and validation: read-only, nothing is written before it passes
+  MeshBounds mb;
+  if (int err = rtmi_mesh_bounds(ns.verts.p, nv, keep.faces.p, nf, s->mesh_scratch.p, &mb, st)) return hip_fail(err);
+  double mag = 0.0, extent = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    mag = std::max(mag, std::max(std::fabs(mb.flo[a]), std::fabs(mb.fhi[a])));
+    extent = std::max(extent, mb.fhi[a] - mb.flo[a]);
+  }
+  if (mb.nonfinite || !std::isfinite(mag) || !std::isfinite(extent))
+    return fail(RT_E_INVALID, "mesh %d: mesh has non-finite vertices", mesh);
+  const double inflate = std::ldexp(std::max(extent, mag), -20) + 1e-30;  // = rt_bvh.cpp
+  lap(1);
+  // 2.-4. records, normals and node boxes into copies of the scene's arrays
+  const int64_t nnodes = s->num_nodes;
+  if ((rc = copy_dev(ns.tree, s->f32.tree, st)) || (rc = copy_dev(ns.nodes, s->nodes, st)) ||
+      (rc = copy_dev(ns.tris, s->f64.tris, st)) || (rc = copy_dev(ns.n32, s->f32.normals, st)) ||
+      (rc = copy_dev(ns.n64, s->f64.normals, st)))
+    return rc;
+  lap(2);
+  TriFast* fast = reinterpret_cast<TriFast*>(ns.tree.p + nnodes) + keep.tri_base;
+  if (!pack_triangles_device(ns.verts.p, keep.faces.p, keep.order.p, nf, fast, ns.tris.p + keep.tri_base, st))
+    return fail(RT_E_DEVICE, "mesh %d: triangle packing failed", mesh);
+  if (int err = rtmi_mesh_normals(ns.verts.p, keep.faces.p, normals ? ns.given.p : nullptr, nf,
+                                  ns.n64.p + 3 * keep.tri_base, ns.n32.p + 3 * keep.tri_base, st))
+    return hip_fail(err);
+  lap(3);
+  if (int err = rtmi_mesh_refit(ns.verts.p, keep.faces.p, keep.order.p, inflate, keep.node_base, keep.node_count,
+                                keep.tri_base, s->refit_parent.p, s->refit_arrivals.p + keep.node_base, ns.nodes.p,
+                                ns.tree.p, st))
+    return hip_fail(err);
+  lap(4);
+  // 5. the binned faces, when this is the only mesh object's mesh
+  const bool binned = s->shadow_mesh >= 0 && s->binnable && s->obj_meta[(size_t)s->shadow_mesh].mesh == mesh;
+  if (binned) {
+    if ((rc = ns.bin.alloc((size_t)nf))) return rc;
+    if (int err = rtmi_mesh_bins(ns.verts.p, keep.faces.p, keep.order.p, nf,
+                                 (nnodes + keep.tri_base) * (int64_t)sizeof(TriFast), ns.bin.p, st))
+      return hip_fail(err);
+  }
+  // 6. the records that hold the mesh's box (calcAABB), as rt_scene_create fills them
+  std::vector<DevMesh<float>> dm32(s->h_dm32);
+  std::vector<DevMesh<double>> dm64(s->h_dm64);
+  std::vector<FMesh> fm(s->h_fm);
+  std::vector<FObj> fo(s->h_fo);
+  std::vector<ObjBox> boxes(s->obj_boxes);
+  for (int k = 0; k < 3; ++k) {
+    dm32[(size_t)mesh].lo[k] = (float)mb.alo[k];
+    dm32[(size_t)mesh].hi[k] = (float)mb.ahi[k];
+    dm64[(size_t)mesh].lo[k] = mb.alo[k];
+    dm64[(size_t)mesh].hi[k] = mb.ahi[k];
+    fm[(size_t)mesh].lo[k] = dm32[(size_t)mesh].lo[k];
+    fm[(size_t)mesh].hi[k] = dm32[(size_t)mesh].hi[k];
+  }
+  for (size_t i = 0; i < s->obj_meta.size(); ++i) {
+    if (s->obj_meta[i].mesh != mesh) continue;
+    for (int k = 0; k < 3; ++k) {
+      fo[i].lo[k] = (float)dm32[(size_t)mesh].lo[k];
+      fo[i].hi[k] = (float)dm32[(size_t)mesh].hi[k];
+    }
+    if (s->objbins) {
+      boxes[i] = ObjBox{};
+      world_obj_box(RT_MESH, s->obj_meta[i].w2o, mb.alo, mb.ahi, &boxes[i]);
+    }
+  }
+  if ((rc = ns.dm64.upload(dm64)) || (rc = ns.fm.upload(fm)) || (rc = ns.fo.upload(fo))) return rc;
+  if (s->objbins) {
+    std::vector<DevObjBox> ob;
+    dev_obj_boxes(boxes, ob);
+    if ((rc = ns.objbox.upload(ob))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  lap(4);
+  // 7. the lights over the new faces and boxes: staged, so that a failure
+  // leaves the scene as it was
+  double old_lo[3], old_hi[3];
+  const double old_scale = s->bin_scale;
+  const auto stage = [&] {
+    if (binned) {
+      std::swap(s->bin_dev, ns.bin);
+      for (int k = 0; k < 3; ++k) {
+        std::swap(s->mesh_lo[k], old_lo[k]);
+        std::swap(s->mesh_hi[k], old_hi[k]);
+      }
+    }
+    std::swap(s->obj_boxes, boxes);
+  };
+  for (int k = 0; k < 3; ++k) {
+    old_lo[k] = mb.alo[k];
+    old_hi[k] = mb.ahi[k];
+  }
+  stage();
+  if (binned) s->bin_scale = 0.0;  // of the old faces: reduced again on demand
+  LightState ls;
+  const bool was_timed = s->relight_timed;
+  s->relight_timed = false;
+  rc = build_lights(s, s->light_desc.data(), s->nlight, true, &ls);
+  s->relight_timed = was_timed;
+  if (rc != RT_OK) {
+    stage();
+    s->bin_scale = old_scale;
+    ls.release();
+    return rc;
+  }
+  const float keep_ms[6] = {s->relight_ms[0], s->relight_ms[1], s->relight_ms[2],
+                            s->relight_ms[3], s->relight_ms[4], s->relight_ms[5]};
+  adopt_lights(s, &ls);
+  std::copy(keep_ms, keep_ms + 6, s->relight_ms);
+  ls.release();
+  std::swap(s->f32.tree, ns.tree);
+  std::swap(s->nodes, ns.nodes);
+  std::swap(s->f64.tris, ns.tris);
+  std::swap(s->f32.normals, ns.n32);
+  std::swap(s->f64.normals, ns.n64);
+  std::swap(s->f64.meshes, ns.dm64);
+  std::swap(s->f32.meshes, ns.fm);
+  std::swap(s->f32.objs, ns.fo);
+  if (s->objbins) std::swap(s->objbox_dev, ns.objbox);
+  std::swap(keep.verts, ns.verts);
+  keep.normals_given = normals != nullptr;
+  s->h_dm32.swap(dm32);
+  s->h_dm64.swap(dm64);
+  s->h_fm.swap(fm);
+  s->h_fo.swap(fo);
+  s->bin_tris_stale = s->bin_tris_stale || binned;
+  s->sh64.release();  // formed from the old faces: rebuilt on demand
+  s->sh64_ready = false;
+  s->orders.clear();  // the measured launch orders were the old geometry's
+  lap(5);
+  if (timed) std::copy(ms, ms + 6, s->mesh_ms);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_scene_set_mesh_vertices(rt_scene* s, int32_t mesh, const double* vertices, int64_t num_vertices,
+                                          const double* normals) {
+  return set_mesh_vertices(s, mesh, vertices, num_vertices, normals, false, nullptr);
+}
+
+extern "C" int rt_scene_set_mesh_vertices_device(rt_scene* s, int32_t mesh, const double* d_vertices,
+                                                 int64_t num_vertices, const double* d_normals, void* hip_stream) {
+  return set_mesh_vertices(s, mesh, d_vertices, num_vertices, d_normals, true, (hipStream_t)hip_stream);
 }
 
 namespace {
@@ -3303,6 +3629,7 @@ extern "C" int64_t rtmi_test_host_lists(rt_scene* s, int32_t w, int32_t h, doubl
   if (!s->binnable) return -1;
   PixelBinsHost hb;
   const char* why = "";
+  if (refresh_bin_tris(s) != RT_OK) return -1;
   if (!build_pixel_bins(s->bin_tris, s->mesh_o2w, s->mesh_w2o, s->c2w, s->fov, w, h, &hb, &why)) return -1;
   const size_t npx = (size_t)w * (size_t)h;
   refresh_host_lists(s);  // (after a relight the prefix sums are on the device only)
@@ -3379,5 +3706,344 @@ extern "C" int rtmi_test_relight_passes(rt_scene* s, int32_t enable, float ms[6]
   std::lock_guard<std::mutex> lk(s->mu);
   if (ms) std::copy(s->relight_ms, s->relight_ms + 6, ms);
   s->relight_timed = enable != 0;
+  return RT_OK;
+}
+
+// ---- mesh updates (rt_scene_set_mesh_vertices) ----------------------------
+
+namespace {
+
+struct AncBox {
+  float lo[3], hi[3];
+};
+
+// faces below `node` whose float64 bounds, inflated, leave one of `anc`
+int64_t uncontained(const BvhResult& r, const double* v, const int32_t* f, double inflate, int32_t node,
+                    std::vector<AncBox>& anc) {
+  int64_t bad = 0;
+  const BvhNode& nd = r.nodes[(size_t)node];
+  for (int slot = 0; slot < 2; ++slot) {
+    const int32_t c = slot ? nd.c1 : nd.c0, n = slot ? nd.n1 : nd.n0;
+    AncBox a;
+    for (int k = 0; k < 3; ++k) {
+      a.lo[k] = slot ? nd.lo1[k] : nd.lo0[k];
+      a.hi[k] = slot ? nd.hi1[k] : nd.hi0[k];
+    }
+    anc.push_back(a);
+    if (n == 0) {
+      if (c > 0) bad += uncontained(r, v, f, inflate, c, anc);
+    } else {
+      for (int32_t j = c; j < c + n; ++j) {
+        const int32_t* fi = &f[3 * (size_t)r.order[(size_t)j]];
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) {
+          double lo = INFINITY, hi = -INFINITY;
+          for (int q = 0; q < 3; ++q) {
+            lo = std::min(lo, v[3 * (size_t)fi[q] + k]);
+            hi = std::max(hi, v[3 * (size_t)fi[q] + k]);
+          }
+          for (const AncBox& b : anc) ok = ok && (double)b.lo[k] <= lo - inflate && (double)b.hi[k] >= hi + inflate;
+        }
+        bad += ok ? 0 : 1;
+      }
+    }
+    anc.pop_back();
+  }
+  return bad;
+}
+
+}  // namespace
+
+// CPU only: a tree built by the host SAH builder on vertices A, refitted
+// (refit_bvh) to vertices B. out[0]: validate_bvh passes (1 / 0); out[1]: the
+// faces whose float64 bounds, inflated by B's margin, are not inside every
+// ancestor's child box; out[2]: the node bytes that differ from the tree built
+// on A (0 when B == A). RT_E_INVALID when the build or the refit declines.
+extern "C" int rtmi_test_refit_host(const double* va, const double* vb, int64_t nv, const int32_t* faces, int64_t nf,
+                                    int64_t out[3]) {
+  if (!va || !vb || !faces || !out || nv <= 0 || nf <= 0) return fail(RT_E_INVALID, "bad argument");
+  for (int64_t k = 0; k < 3 * nf; ++k)
+    if (faces[k] < 0 || faces[k] >= nv) return fail(RT_E_INVALID, "face index out of range");
+  BvhResult built;
+  const char* err = "";
+  BvhBuildParams prm;
+  if (!build_bvh(va, faces, nf, prm, &built, &err)) return fail(RT_E_INVALID, "%s", err);
+  BvhResult r = built;
+  double inflate = 0.0;
+  if (!refit_bvh(vb, faces, nf, &r, &err) || !bvh_margin(vb, faces, nf, &inflate)) return fail(RT_E_INVALID, "%s", err);
+  out[0] = validate_bvh(r, nf, &err) ? 1 : 0;
+  std::vector<AncBox> anc;
+  out[1] = uncontained(r, vb, faces, inflate, 0, anc);
+  out[2] = 0;
+  const unsigned char* pa = reinterpret_cast<const unsigned char*>(built.nodes.data());
+  const unsigned char* pb = reinterpret_cast<const unsigned char*>(r.nodes.data());
+  for (size_t k = 0; k < built.nodes.size() * sizeof(BvhNode); ++k) out[2] += pa[k] != pb[k] ? 1 : 0;
+  return RT_OK;
+}
+
+namespace {
+
+template <class T>
+bool download(const T* p, size_t n, std::vector<T>& h) {
+  h.resize(n);
+  return n == 0 || hipMemcpy(h.data(), p, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+template <class T>
+int64_t diff_bytes(const T& a, const T& b) {
+  return std::memcmp(&a, &b, sizeof(T)) != 0 ? 1 : 0;
+}
+
+// equal bytes, or both NaN (a degenerate face's 0/0 normal: its sign bit
+// differs between the host and the device, and nothing reads it)
+template <class T>
+int64_t diff_num(T a, T b) {
+  return std::memcmp(&a, &b, sizeof(T)) != 0 && !(a != a && b != b) ? 1 : 0;
+}
+
+uint64_t fnv(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
+  const unsigned char* b = static_cast<const unsigned char*>(p);
+  for (size_t k = 0; k < n; ++k) h = (h ^ b[k]) * 1099511628211ull;
+  return h;
+}
+
+}  // namespace
+
+// The host create path on the scene's current vertices (records, normals,
+// calcAABB, object boxes, refit_bvh on the scene's topology) against the
+// device-resident arrays, byte for byte (normals: any NaN equals any NaN).
+// out[k]: differing elements of 0 TriFast, 1 TriF64, 2 the float32 normals,
+// 3 the float64 normals, 4 bin_dev, 5 the float64 kernels' node boxes, 6 the
+// float32 tree's node boxes, 7 child references and counts (both trees),
+// 8 DevMesh<float> (host only: the source of FMesh / FObj), 9 DevMesh<double>,
+// 10 FMesh, 11 FObj, 12 objbox_dev, 13 the bins' mesh box; 14, 15: zero.
+extern "C" int rtmi_test_mesh_update_diff(rt_scene* s, int64_t out[16]) {
+  if (!s || !out) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  const int prev = device_of_current();
+  if (prev != s->device) (void)hipSetDevice(s->device);
+  struct Restore {
+    int prev, dev;
+    ~Restore() {
+      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+  } restore{prev, s->device};
+  HIP_TRY(hipDeviceSynchronize());
+  std::fill(out, out + 16, 0);
+  const int64_t nnodes = s->num_nodes, ntri = s->num_triangles;
+  std::vector<BvhNode> tree, nodes;
+  std::vector<TriF64> tris;
+  std::vector<float> n32;
+  std::vector<double> n64;
+  std::vector<DevBinTri> bins;
+  if (!download(s->f32.tree.p, (size_t)(nnodes + ntri), tree) || !download(s->nodes.p, (size_t)nnodes, nodes) ||
+      !download(s->f64.tris.p, (size_t)ntri, tris) || !download(s->f32.normals.p, (size_t)ntri * 3, n32) ||
+      !download(s->f64.normals.p, (size_t)ntri * 3, n64) ||
+      !download(s->bin_dev.p, s->binnable ? s->bin_tris.size() : 0, bins))
+    return fail(RT_E_DEVICE, "reading the mesh arrays back failed");
+  const TriFast* fast = reinterpret_cast<const TriFast*>(tree.data() + nnodes);
+  std::vector<DevMesh<float>> dm32(s->h_dm32);
+  std::vector<DevMesh<double>> dm64(s->h_dm64);
+  std::vector<FMesh> fm(s->h_fm);
+  std::vector<FObj> fo(s->h_fo);
+  std::vector<ObjBox> boxes(s->obj_boxes);
+  const int32_t bin_mesh = s->shadow_mesh >= 0 && s->binnable ? s->obj_meta[(size_t)s->shadow_mesh].mesh : -1;
+  for (int m = 0; m < s->nmesh; ++m) {
+    const rt_scene::MeshKeep& keep = s->mesh_keep[(size_t)m];
+    std::vector<double> v;
+    std::vector<int32_t> f, order;
+    if (!download(keep.verts.p, (size_t)keep.nv * 3, v) || !download(keep.faces.p, (size_t)keep.nf * 3, f) ||
+        !download(keep.order.p, (size_t)keep.nf, order))
+      return fail(RT_E_DEVICE, "reading the mesh arrays back failed");
+    // calcAABB and the records that hold it
+    double bb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = 0; i < keep.nv; ++i)
+      for (int k = 0; k < 3; ++k) {
+        const double x = v[3 * (size_t)i + k];
+        if (x < bb[k]) bb[k] = x;
+        if (x > bb[3 + k]) bb[3 + k] = x;
+      }
+    for (int k = 0; k < 3; ++k) {
+      dm32[(size_t)m].lo[k] = (float)bb[k];
+      dm32[(size_t)m].hi[k] = (float)bb[3 + k];
+      dm64[(size_t)m].lo[k] = bb[k];
+      dm64[(size_t)m].hi[k] = bb[3 + k];
+      fm[(size_t)m].lo[k] = dm32[(size_t)m].lo[k];
+      fm[(size_t)m].hi[k] = dm32[(size_t)m].hi[k];
+    }
+    for (size_t i = 0; i < s->obj_meta.size(); ++i) {
+      if (s->obj_meta[i].mesh != m) continue;
+      for (int k = 0; k < 3; ++k) {
+        fo[i].lo[k] = dm32[(size_t)m].lo[k];
+        fo[i].hi[k] = dm32[(size_t)m].hi[k];
+      }
+      if (s->objbins) {
+        boxes[i] = ObjBox{};
+        world_obj_box(RT_MESH, s->obj_meta[i].w2o, bb, bb + 3, &boxes[i]);
+      }
+    }
+    if (m == bin_mesh)
+      for (int k = 0; k < 3; ++k) out[13] += diff_bytes(s->mesh_lo[k], bb[k]) + diff_bytes(s->mesh_hi[k], bb[3 + k]);
+    // records and normals in leaf order (k_pack's and rt_scene_create's operations)
+    for (int64_t i = 0; i < keep.nf; ++i) {
+      const int32_t face = order[(size_t)i];
+      const int32_t* fi = &f[3 * (size_t)face];
+      const double* v0 = &v[3 * (size_t)fi[0]];
+      const double* v1 = &v[3 * (size_t)fi[1]];
+      const double* v2 = &v[3 * (size_t)fi[2]];
+      double e1[3], e2[3];
+      for (int k = 0; k < 3; ++k) {
+        e1[k] = v1[k] - v0[k];
+        e2[k] = v2[k] - v0[k];
+      }
+      const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                           e1[0] * e2[1] - e1[1] * e2[0]};
+      TriFast t;
+      TriF64 d;
+      std::memset(&t, 0, sizeof t);
+      std::memset(&d, 0, sizeof d);
+      for (int k = 0; k < 3; ++k) {
+        t.v0[k] = (float)v0[k];
+        t.e2[k] = (float)e2[k];
+        t.e1n[k] = (float)-e1[k];
+        t.nn[k] = (float)-n[k];
+        d.v0[k] = v0[k];
+        d.e1[k] = e1[k];
+        d.e2[k] = e2[k];
+      }
+      t.id = face;
+      d.id = face;
+      out[0] += diff_bytes(fast[keep.tri_base + i], t);
+      out[1] += diff_bytes(tris[(size_t)(keep.tri_base + i)], d);
+      if (m == bin_mesh) {
+        DevBinTri b;
+        std::memset(&b, 0, sizeof b);
+        for (int q = 0; q < 3; ++q)
+          for (int k = 0; k < 3; ++k) b.v[q][k] = v[3 * (size_t)fi[q] + k];
+        b.rec = (int32_t)((nnodes + keep.tri_base + i) * (int64_t)sizeof(TriFast));
+        b.face = face;
+        out[4] += diff_bytes(bins[(size_t)i], b);
+      }
+    }
+    for (int64_t fidx = 0; fidx < keep.nf; ++fidx) {
+      const size_t at = 3 * (size_t)(keep.tri_base + fidx);
+      double nr[3];
+      if (keep.normals_given) {  // the caller's values are what the float64 array holds
+        for (int k = 0; k < 3; ++k) nr[k] = n64[at + k];
+      } else {
+        const double* p0 = &v[3 * (size_t)f[3 * fidx + 0]];
+        const double* p1 = &v[3 * (size_t)f[3 * fidx + 1]];
+        const double* p2 = &v[3 * (size_t)f[3 * fidx + 2]];
+        const double ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
+        const double bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
+        const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+        double dd = 0.0;
+        dd = dd + cx * cx;
+        dd = dd + cy * cy;
+        dd = dd + cz * cz;
+        const double len = std::sqrt(dd);
+        nr[0] = cx / len;
+        nr[1] = cy / len;
+        nr[2] = cz / len;
+      }
+      for (int k = 0; k < 3; ++k) {
+        out[3] += diff_num(n64[at + k], nr[k]);
+        out[2] += diff_num(n32[at + k], (float)nr[k]);
+      }
+    }
+    // the host refit of this mesh's nodes as created
+    if (keep.node_count > 0) {
+      BvhResult r;
+      r.order = order;
+      r.nodes.assign(s->h_nodes.begin() + keep.node_base, s->h_nodes.begin() + keep.node_base + keep.node_count);
+      for (BvhNode& nd : r.nodes) {
+        if (nd.n0 == 0 && nd.c0 >= 0) nd.c0 -= keep.node_base;
+        if (nd.n1 == 0 && nd.c1 >= 0) nd.c1 -= keep.node_base;
+        if (nd.n0 > 0) nd.c0 -= (int32_t)keep.tri_base;
+        if (nd.n1 > 0) nd.c1 -= (int32_t)keep.tri_base;
+      }
+      const char* err = "";
+      if (!refit_bvh(v.data(), f.data(), keep.nf, &r, &err)) return fail(RT_E_INVALID, "mesh %d: %s", m, err);
+      const int32_t kB = (int32_t)sizeof(BvhNode);
+      for (int32_t k = 0; k < keep.node_count; ++k) {
+        const BvhNode& want = r.nodes[(size_t)k];
+        const BvhNode& topo = s->h_nodes[(size_t)(keep.node_base + k)];
+        const BvhNode& a = nodes[(size_t)(keep.node_base + k)];
+        const BvhNode& b = tree[(size_t)(keep.node_base + k)];
+        out[5] += std::memcmp(a.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+        out[6] += std::memcmp(b.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+        out[7] += (a.c0 != topo.c0) + (a.c1 != topo.c1) + (a.n0 != topo.n0) + (a.n1 != topo.n1);
+        out[7] += (b.c0 != (topo.n0 > 0 ? (int32_t)nnodes + topo.c0 : topo.c0) * kB) +
+                  (b.c1 != (topo.n1 > 0 ? (int32_t)nnodes + topo.c1 : topo.c1) * kB) + (b.n0 != topo.n0) +
+                  (b.n1 != topo.n1);
+      }
+    }
+  }
+  std::vector<DevMesh<double>> d_dm64;
+  std::vector<FMesh> d_fm;
+  std::vector<FObj> d_fo;
+  std::vector<DevObjBox> d_ob, want_ob;
+  if (!download(s->f64.meshes.p, dm64.size(), d_dm64) || !download(s->f32.meshes.p, fm.size(), d_fm) ||
+      !download(s->f32.objs.p, fo.size(), d_fo) || !download(s->objbox_dev.p, s->objbins ? boxes.size() : 0, d_ob))
+    return fail(RT_E_DEVICE, "reading the mesh arrays back failed");
+  for (size_t k = 0; k < dm64.size(); ++k) {
+    out[8] += diff_bytes(s->h_dm32[k], dm32[k]);
+    out[9] += diff_bytes(d_dm64[k], dm64[k]);
+    out[10] += diff_bytes(d_fm[k], fm[k]);
+  }
+  for (size_t k = 0; k < fo.size(); ++k) out[11] += diff_bytes(d_fo[k], fo[k]);
+  if (s->objbins) {
+    dev_obj_boxes(boxes, want_ob);
+    for (size_t k = 0; k < want_ob.size(); ++k) out[12] += diff_bytes(d_ob[k], want_ob[k]);
+  }
+  return RT_OK;
+}
+
+// FNV-1a hashes of the device arrays a mesh update writes, for "nothing else
+// changed" checks: 0 mesh's TriFast records, 1 its TriF64, 2 / 3 its float32 /
+// float64 normals, 4 / 5 its nodes in the float64 / float32 tree, 6 bin_dev,
+// 7 the mesh, object and object-box records of the whole scene.
+extern "C" int rtmi_test_mesh_hash(rt_scene* s, int32_t mesh, uint64_t out[8]) {
+  if (!s || !out || mesh < 0 || mesh >= s->nmesh) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  const int prev = device_of_current();
+  if (prev != s->device) (void)hipSetDevice(s->device);
+  struct Restore {
+    int prev, dev;
+    ~Restore() {
+      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+  } restore{prev, s->device};
+  HIP_TRY(hipDeviceSynchronize());
+  const rt_scene::MeshKeep& keep = s->mesh_keep[(size_t)mesh];
+  const size_t nf = (size_t)keep.nf, nn = (size_t)keep.node_count;
+  bool ok = true;
+  const auto hash_dev = [&](const void* p, size_t bytes, uint64_t h = 1469598103934665603ull) {
+    std::vector<unsigned char> buf;
+    ok = ok && download(static_cast<const unsigned char*>(p), p ? bytes : 0, buf);
+    return fnv(buf.data(), buf.size(), h);
+  };
+  out[0] = hash_dev(reinterpret_cast<const TriFast*>(s->f32.tree.p + s->num_nodes) + keep.tri_base, nf * sizeof(TriFast));
+  out[1] = hash_dev(s->f64.tris.p + keep.tri_base, nf * sizeof(TriF64));
+  out[2] = hash_dev(s->f32.normals.p + 3 * keep.tri_base, nf * 3 * sizeof(float));
+  out[3] = hash_dev(s->f64.normals.p + 3 * keep.tri_base, nf * 3 * sizeof(double));
+  out[4] = hash_dev(s->nodes.p + keep.node_base, nn * sizeof(BvhNode));
+  out[5] = hash_dev(s->f32.tree.p + keep.node_base, nn * sizeof(BvhNode));
+  out[6] = hash_dev(s->bin_dev.p, s->binnable ? s->bin_tris.size() * sizeof(DevBinTri) : 0);
+  out[7] = hash_dev(s->f64.meshes.p, (size_t)s->nmesh * sizeof(DevMesh<double>));
+  out[7] = hash_dev(s->f32.meshes.p, (size_t)s->nmesh * sizeof(FMesh), out[7]);
+  out[7] = hash_dev(s->f32.objs.p, (size_t)s->nobj * sizeof(FObj), out[7]);
+  out[7] = hash_dev(s->objbox_dev.p, s->objbins ? (size_t)s->nobj * sizeof(DevObjBox) : 0, out[7]);
+  return ok ? RT_OK : fail(RT_E_DEVICE, "reading the mesh arrays back failed");
+}
+
+// enable: time the passes of the next updates (the stream is waited for after
+// each). ms (may be null): the last timed update's copy-in, bounds, buffer
+// copies, records + normals, refit + bins + box records, lights.
+extern "C" int rtmi_test_mesh_update_passes(rt_scene* s, int32_t enable, float ms[6]) {
+  if (!s) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (ms) std::copy(s->mesh_ms, s->mesh_ms + 6, ms);
+  s->mesh_timed = enable != 0;
   return RT_OK;
 }

@@ -185,6 +185,9 @@ SIGNATURES = {
     "rt_scene_get_info": (C.c_int, [_P, C.POINTER(rt_scene_info)]),
     "rt_scene_set_camera": (C.c_int, [_P, C.POINTER(C.c_double), C.c_double]),
     "rt_scene_set_lights": (C.c_int, [_P, C.POINTER(rt_light_desc), C.c_int32]),
+    "rt_scene_set_mesh_vertices": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.c_int64,
+                                             C.POINTER(C.c_double)]),
+    "rt_scene_set_mesh_vertices_device": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P]),
     "rt_render_lines": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(C.c_float), C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.POINTER(rt_stats)]),
@@ -218,6 +221,8 @@ SIGNATURES = {
                                         C.POINTER(rt_stats)]),
     "rt_multi_set_camera": (C.c_int, [_P, C.POINTER(C.c_double), C.c_double]),
     "rt_multi_set_lights": (C.c_int, [_P, C.POINTER(rt_light_desc), C.c_int32]),
+    "rt_multi_set_mesh_vertices": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.c_int64,
+                                             C.POINTER(C.c_double)]),
     "rt_multi_destroy": (C.c_int, [_P]),
     "rt_queue_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_queue_start": (C.c_int, [_P]),

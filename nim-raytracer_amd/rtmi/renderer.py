@@ -43,6 +43,7 @@ class DeviceScene:
         h = C.c_void_p()
         check(lib().rt_scene_create(C.byref(flat.desc), C.byref(h)))
         self.h = h
+        self._mesh_ids = [id(g) for g in flat._meshes]  # rt_scene_desc.meshes order (set_mesh_vertices)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -76,6 +77,40 @@ class DeviceScene:
         scene then renders exactly as one created with these lights."""
         ls = list(self.scene.lights if lights is None else lights)
         check(lib().rt_scene_set_lights(self.h, flatten_lights(ls), len(ls)))
+
+    def mesh_index(self, mesh):
+        """The rt_scene_desc.meshes index of `mesh`: an index, or one of the
+        TriangleMesh objects this DeviceScene was created from."""
+        if isinstance(mesh, (int, np.integer)):
+            return int(mesh)
+        try:
+            return self._mesh_ids.index(id(mesh))
+        except ValueError:
+            raise ValueError("mesh is not one of this DeviceScene's TriangleMesh objects") from None
+
+    def set_mesh_vertices(self, mesh, vertices, normals=None, stream=None):
+        """New vertex positions for one mesh (rt_scene_set_mesh_vertices):
+        `mesh` is an index or the scene's TriangleMesh, vertices (N, 3)
+        float64 with the N the mesh was created with, normals (F, 3) or None
+        (calcNormals, as at create). numpy arrays take the host form; float64
+        CUDA tensors the device form, read behind `stream` (None: torch's
+        current stream). Faces, BVH topology, camera, lights and the other
+        meshes stay; the scene then answers exactly as one created with
+        these vertices."""
+        m = self.mesh_index(mesh)
+        if _is_host(vertices):
+            v = _host_f64(vertices, (-1, 3))
+            n = None if normals is None else _host_f64(normals, (-1, 3))
+            check(lib().rt_scene_set_mesh_vertices(self.h, m, _dptr(v), v.shape[0], _dptr(n)))
+            return
+        nv = _dev_f64(vertices, None, 3)
+        if normals is not None:
+            if _is_host(normals):
+                raise ValueError("vertices and normals must both be host arrays or both device tensors")
+            _dev_f64(normals, None, 3)
+        check(lib().rt_scene_set_mesh_vertices_device(
+            self.h, m, C.c_void_p(vertices.data_ptr()), nv,
+            C.c_void_p(normals.data_ptr()) if normals is not None else None, _stream(stream)))
 
     # -- host framebuffer (the pool-compatible path) ----------------------
     def render_lines(self, opts: Options, fb, y0, y1, step=1, maxStep=1) -> Stats:
@@ -279,7 +314,7 @@ def _shape_key(scene: Scene):
     bounds (all of vmin / vmax, geom.nim:169-170), mesh sizes, background —
     the fingerprint INTEGRATION.md's Nim binding (shapeHash) keeps; a change
     rebuilds the device scene. Mesh vertices edited in place (same sizes) are
-    not hashed per call: invalidateScene."""
+    not hashed per call: updateMesh (or invalidateScene, which rebuilds)."""
     from .scene import Box, Sphere, TriangleMesh
     parts = []
     for o in scene.objects:
@@ -416,6 +451,16 @@ class _DeviceCache:
         if stale is not None:
             stale.close()
 
+    def update_mesh(self, scene: Scene, mesh):
+        """Push `mesh`'s current vertices (and normals) to the cached device
+        copy, if there is one: the copy and its handle stay, nothing is
+        rebuilt. Without a copy the next acquire creates from current data."""
+        with self._lock:
+            item = self._entries.get(id(scene))
+            e = item[1] if item is not None and item[0]() is scene else None
+            if e is not None and not e.retired:
+                e.ds.set_mesh_vertices(mesh, mesh.vertices, mesh.normals)
+
     def _collected(self, key):
         with self._lock:
             item = self._entries.get(key)
@@ -447,8 +492,17 @@ def heldDeviceScene(scene: Scene, device=0):
 
 
 def invalidateScene(scene: Scene):
-    """After editing mesh vertices / faces in place (same sizes)."""
+    """After editing mesh faces in place (same sizes): the device copy is
+    rebuilt by the next call. For vertices alone updateMesh is far cheaper."""
     _cache.invalidate(scene)
+
+
+def updateMesh(scene: Scene, mesh):
+    """After editing `mesh.vertices` (one of scene's TriangleMesh objects) in
+    place: the cached device copy takes the new positions
+    (rt_scene_set_mesh_vertices: records, normals, a BVH refit and the light
+    grids on the device) and keeps its handle."""
+    _cache.update_mesh(scene, mesh)
 
 
 def renderLine(scene, opts: Options, fb, y, step=1, maxStep=1) -> Stats:
@@ -503,6 +557,7 @@ class MultiDeviceScene:
         h = C.c_void_p()
         check(lib().rt_multi_create(C.byref(flat.desc), arr, len(self.devices), int(band_h), C.byref(h)))
         self.h = h
+        self._mesh_ids = [id(g) for g in flat._meshes]
 
     def set_camera(self, cameraToWorld, fov):
         """rt_scene_set_camera on every rank's scene."""
@@ -513,6 +568,15 @@ class MultiDeviceScene:
         """rt_scene_set_lights on every rank's scene."""
         ls = list(lights)
         check(lib().rt_multi_set_lights(self.h, flatten_lights(ls), len(ls)))
+
+    def set_mesh_vertices(self, mesh, vertices, normals=None):
+        """rt_scene_set_mesh_vertices on every rank's scene (host arrays);
+        `mesh` is an index or one of the Scene's TriangleMesh objects."""
+        if not isinstance(mesh, (int, np.integer)):
+            mesh = self._mesh_ids.index(id(mesh))
+        v = _host_f64(vertices, (-1, 3))
+        n = None if normals is None else _host_f64(normals, (-1, 3))
+        check(lib().rt_multi_set_mesh_vertices(self.h, int(mesh), _dptr(v), v.shape[0], _dptr(n)))
 
     def render_frame(self, opts: Options, fb) -> Stats:
         """Whole frame into a host (h, w, 3) float32 array."""
@@ -718,4 +782,4 @@ def _stream(stream):
 
 
 __all__ = ["DeviceScene", "RtmiError", "band_rows", "device_count", "deviceScene", "heldDeviceScene", "initRenderer", "invalidateScene",
-           "ppm_encode_device", "renderLine", "render_frame", "unshard_bands_device", "write_ppm_device"]
+           "ppm_encode_device", "renderLine", "render_frame", "unshard_bands_device", "updateMesh", "write_ppm_device"]
