@@ -95,7 +95,7 @@ bool pixel_camera(const double o2w[16], const double w2o[16], const double c2w[1
                   int height, bg::PixCam* out) {
   if (!invert4(c2w, out->w2c)) return false;
   std::memcpy(out->o2w, o2w, sizeof out->o2w);
-  // camera constants of the float32 kernel (rtmi.cpp fill_fast): a camera-space
+  // camera constants of the float32 kernel (rt_render.cpp fast_camera): a camera-space
   // direction (cx, cy, -1) is the sample at px = w/2 + cx/a, py = h/2 - cy/c
   const double f = std::tan(fov_deg * (3.14159265358979323846 / 180.0) / 2);
   const double r = (double)width / (double)height;

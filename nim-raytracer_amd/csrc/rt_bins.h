@@ -32,7 +32,7 @@ namespace rtmi {
 // holds for the kernels' camera rays as long as every sample offset lies in
 // [0, 1) — true for all of sampling.nim's samplers (akNone: 0, grid:
 // (i + 1/2)/m, jittered / multi-jittered / correlated: [0, 1)), checked on
-// the host (rtmi.cpp sampler_in_pixel) before any bin is handed to a kernel —
+// the host (rt_render.cpp sampler_in_pixel) before any bin is handed to a kernel —
 // and the margin is far above the float32 error of the ray set-up.
 constexpr double kPixelMargin = 0.05;
 

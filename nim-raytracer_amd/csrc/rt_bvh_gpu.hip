@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "rt_bvh.h"
+#include "rt_hip.h"
 
 namespace rtmi {
 namespace {
@@ -366,15 +367,6 @@ __global__ __launch_bounds__(kBlock) void k_emit(int32_t nf, int32_t ninner, con
   out[me] = nd;
 }
 
-template <class T>
-struct Dev {
-  T* p = nullptr;
-  ~Dev() {
-    if (p) (void)hipFree(p);
-  }
-  bool alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess; }
-};
-
 unsigned grid(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 
@@ -455,18 +447,18 @@ bool build_bvh_device(const double* d_vin, const int32_t* d_fin, int64_t nf, con
 
   const double* d_v = d_vin;
   const int32_t* d_f = d_fin;
-  Dev<unsigned long long> d_bounds, d_key, d_key2, d_flags, d_pos, d_tot;
-  Dev<Box32> d_box, d_cl_box[2];
-  Dev<int32_t> d_id, d_id2, d_cl_id[2], d_nn, d_parent, d_visits, d_slot, d_index, d_order, d_depth;
-  Dev<int2> d_children;
-  Dev<Box32> d_node_box;
-  Dev<NodeInfo> d_info;
-  if (!d_bounds.alloc(6) || !d_key.alloc(n) ||
-      !d_key2.alloc(n) || !d_flags.alloc(n) || !d_pos.alloc(n) || !d_tot.alloc(1) || !d_box.alloc(n) ||
-      !d_cl_box[0].alloc(n) || !d_cl_box[1].alloc(n) || !d_id.alloc(n) || !d_id2.alloc(n) ||
-      !d_cl_id[0].alloc(n) || !d_cl_id[1].alloc(n) || !d_nn.alloc(n) || !d_parent.alloc(nnodes) ||
-      !d_visits.alloc(n) || !d_slot.alloc(nnodes) || !d_index.alloc(nnodes) || !d_order.alloc(n) ||
-      !d_depth.alloc(1) || !d_children.alloc(n) || !d_node_box.alloc(nnodes) || !d_info.alloc(nnodes)) {
+  DevBuf<unsigned long long> d_bounds, d_key, d_key2, d_flags, d_pos, d_tot;
+  DevBuf<Box32> d_box, d_cl_box[2];
+  DevBuf<int32_t> d_id, d_id2, d_cl_id[2], d_nn, d_parent, d_visits, d_slot, d_index, d_order, d_depth;
+  DevBuf<int2> d_children;
+  DevBuf<Box32> d_node_box;
+  DevBuf<NodeInfo> d_info;
+  if (d_bounds.alloc(6) || d_key.alloc(n) ||
+      d_key2.alloc(n) || d_flags.alloc(n) || d_pos.alloc(n) || d_tot.alloc(1) || d_box.alloc(n) ||
+      d_cl_box[0].alloc(n) || d_cl_box[1].alloc(n) || d_id.alloc(n) || d_id2.alloc(n) ||
+      d_cl_id[0].alloc(n) || d_cl_id[1].alloc(n) || d_nn.alloc(n) || d_parent.alloc(nnodes) ||
+      d_visits.alloc(n) || d_slot.alloc(nnodes) || d_index.alloc(nnodes) || d_order.alloc(n) ||
+      d_depth.alloc(1) || d_children.alloc(n) || d_node_box.alloc(nnodes) || d_info.alloc(nnodes)) {
     *err = "device BVH build: out of device memory";
     return false;
   }
@@ -508,8 +500,8 @@ bool build_bvh_device(const double* d_vin, const int32_t* d_fin, int64_t nf, con
                                    st));
   DEV_OK(rocprim::exclusive_scan(nullptr, scan_bytes, d_flags.p, d_pos.p, 0ull, (size_t)n,
                                  rocprim::plus<unsigned long long>(), st));
-  Dev<unsigned char> d_tmp;
-  if (!d_tmp.alloc(std::max(sort_bytes, scan_bytes))) {
+  DevBuf<unsigned char> d_tmp;
+  if (d_tmp.alloc(std::max(sort_bytes, scan_bytes))) {
     *err = "device BVH build: out of device memory";
     return false;
   }
@@ -579,8 +571,8 @@ bool build_bvh_device(const double* d_vin, const int32_t* d_fin, int64_t nf, con
   k_layout<<<grid(nnodes), kBlock, 0, st>>>(n, nnodes, d_parent.p, d_children.p, d_info.p, prm.max_leaf, d_slot.p,
                                             d_index.p, d_order.p, d_depth.p);
   const int32_t ninner = ri.leaf ? 0 : ri.inner;
-  Dev<BvhNode> d_out;
-  if (!d_out.alloc(std::max(ninner, 1))) {
+  DevBuf<BvhNode> d_out;
+  if (d_out.alloc(std::max(ninner, 1))) {
     *err = "device BVH build: out of device memory";
     return false;
   }

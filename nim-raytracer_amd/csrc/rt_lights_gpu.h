@@ -1,7 +1,7 @@
 // rt_lights_gpu.h — device builder of the distant lights' mesh grids
 // (rt_scene_set_lights). One call builds one light's grid from the scene's
 // resident faces (rt_frame.h DevBinTri, leaf order) into device buffers of
-// its own: what rt_bins.cpp build_light_grid + grid_occupancy and rtmi.cpp's
+// its own: what rt_bins.cpp build_light_grid + grid_occupancy and rt_scene_lights.cpp's
 // record loops (make_ltri, the cell-order gather) produce on the host, byte
 // for byte — both sides call rt_bins_geom.h's functions, compiled without
 // contraction.

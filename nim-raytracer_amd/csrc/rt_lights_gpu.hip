@@ -38,6 +38,7 @@
 
 #include "rt_bins.h"
 #include "rt_bins_geom.h"
+#include "rt_hip.h"
 #include "rt_lights_gpu.h"
 
 namespace rtmi {
@@ -268,30 +269,17 @@ __global__ __launch_bounds__(kBlock) void k_light_culled(LTri* p, long long n) {
   if (i < n) p[i] = bg::culled_ltri();
 }
 
-template <class T>
-struct Dev {
-  T* p = nullptr;
-  hipError_t alloc(size_t count) {
-    const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) p = nullptr;
-    return e;
-  }
-  T* take() {
-    T* q = p;
-    p = nullptr;
-    return q;
-  }
-  ~Dev() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 unsigned grid_of(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 #define LG_TRY(expr)                     \
   do {                                   \
     const hipError_t e_ = (expr);        \
     if (e_ != hipSuccess) return (int)e_; \
+  } while (0)
+// a DevBuf allocation: these entry points answer with hipError_t values
+#define LG_ALLOC(buf, count)                                          \
+  do {                                                                \
+    if ((buf).alloc(count) != RT_OK) return (int)hipErrorOutOfMemory; \
   } while (0)
 
 // per-pass times of a timed build: events between the passes
@@ -325,8 +313,8 @@ extern "C" int rtmi_lights_scale(const rtmi::DevBinTri* tris, int64_t n, double*
   hipStream_t st = (hipStream_t)stream;
   *scale = 1.0;
   if (n <= 0) return 0;
-  Dev<unsigned long long> red;
-  LG_TRY(red.alloc(RED_WORDS));
+  DevBuf<unsigned long long> red;
+  LG_ALLOC(red, RED_WORDS);
   unsigned long long h[RED_WORDS] = {};
   h[RED_SCALE] = key_of(1.0);
   LG_TRY(hipMemcpyAsync(red.p, h, sizeof h, hipMemcpyHostToDevice, st));
@@ -366,11 +354,11 @@ extern "C" int rtmi_light_grid_build(const rtmi::LightGridJob* job, rtmi::LightG
   const double delta = 1e-5 * job->scale;
   PassClock clock(timed != 0, st);
   // 1. faces
-  Dev<double> proj, box;
-  Dev<unsigned long long> red;
-  LG_TRY(proj.alloc((size_t)n * 6));
-  LG_TRY(box.alloc((size_t)n * 4));
-  LG_TRY(red.alloc(RED_WORDS));
+  DevBuf<double> proj, box;
+  DevBuf<unsigned long long> red;
+  LG_ALLOC(proj, (size_t)n * 6);
+  LG_ALLOC(box, (size_t)n * 4);
+  LG_ALLOC(red, RED_WORDS);
   unsigned long long h[RED_WORDS] = {};
   h[RED_UMIN] = h[RED_VMIN] = key_of(INFINITY);
   h[RED_UMAX] = h[RED_VMAX] = key_of(-INFINITY);
@@ -388,9 +376,9 @@ extern "C" int rtmi_light_grid_build(const rtmi::LightGridJob* job, rtmi::LightG
   const long long ncell = (long long)g.gu * g.gv;
   // 2. count
   clock.mark();
-  Dev<int32_t> cnt, off;
-  LG_TRY(cnt.alloc((size_t)ncell + 1));
-  LG_TRY(off.alloc((size_t)ncell + 1));
+  DevBuf<int32_t> cnt, off;
+  LG_ALLOC(cnt, (size_t)ncell + 1);
+  LG_ALLOC(off, (size_t)ncell + 1);
   LG_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)ncell + 1) * sizeof(int32_t), st));
   long long total = 0;
   if (kept > 0) {
@@ -407,8 +395,8 @@ extern "C" int rtmi_light_grid_build(const rtmi::LightGridJob* job, rtmi::LightG
   {
     size_t bytes = 0;
     LG_TRY(rocprim::exclusive_scan(nullptr, bytes, cnt.p, off.p, 0, (size_t)ncell + 1, rocprim::plus<int32_t>(), st));
-    Dev<unsigned char> tmp;
-    LG_TRY(tmp.alloc(bytes));
+    DevBuf<unsigned char> tmp;
+    LG_ALLOC(tmp, bytes);
     LG_TRY(rocprim::exclusive_scan(tmp.p, bytes, cnt.p, off.p, 0, (size_t)ncell + 1, rocprim::plus<int32_t>(), st));
     LG_TRY(hipStreamSynchronize(st));  // tmp goes
   }
@@ -420,15 +408,15 @@ extern "C" int rtmi_light_grid_build(const rtmi::LightGridJob* job, rtmi::LightG
   // 5. fill, order, pad
   clock.mark();
   const size_t nent = (size_t)total + kBinPad;
-  Dev<int32_t> ent, tmp_i, tmp_cell, sat;
-  Dev<double> tmp_cov;
-  Dev<LTri> grec;
-  LG_TRY(ent.alloc(nent));
-  LG_TRY(grec.alloc(nent));
+  DevBuf<int32_t> ent, tmp_i, tmp_cell, sat;
+  DevBuf<double> tmp_cov;
+  DevBuf<LTri> grec;
+  LG_ALLOC(ent, nent);
+  LG_ALLOC(grec, nent);
   if (total > 0) {
-    LG_TRY(tmp_i.alloc((size_t)total));
-    LG_TRY(tmp_cell.alloc((size_t)total));
-    LG_TRY(tmp_cov.alloc((size_t)total));
+    LG_ALLOC(tmp_i, (size_t)total);
+    LG_ALLOC(tmp_cell, (size_t)total);
+    LG_ALLOC(tmp_cov, (size_t)total);
     LG_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)ncell + 1) * sizeof(int32_t), st));
     LG_TRY(hipMemsetAsync(tmp_i.p, 0, (size_t)total * sizeof(int32_t), st));
     LG_TRY(hipMemsetAsync(tmp_cell.p, 0xff, (size_t)total * sizeof(int32_t), st));
@@ -445,7 +433,7 @@ extern "C" int rtmi_light_grid_build(const rtmi::LightGridJob* job, rtmi::LightG
   // 6. occupancy prefix sums
   clock.mark();
   const size_t nsat = (size_t)(g.gu + 1) * (size_t)(g.gv + 1);
-  LG_TRY(sat.alloc(nsat));
+  LG_ALLOC(sat, nsat);
   LG_TRY(hipMemsetAsync(sat.p, 0, nsat * sizeof(int32_t), st));
   hipLaunchKernelGGL(k_light_sat_rows, dim3(grid_of(g.gv)), dim3(kBlock), 0, st, off.p, g.gu, g.gv, sat.p);
   LG_TRY(hipGetLastError());

@@ -1,0 +1,243 @@
+// rt_queries.cpp — ray queries (rt_trace_rays* / rt_pick_pixels*): float64
+// closest hit, any hit and pixel picking on a scene, beside its render calls.
+#include <cmath>
+#include <cstring>
+
+#include "rt_query.h"
+#include "rt_scene.h"
+
+namespace {
+
+constexpr uint32_t kQueryFlags = RT_QUERY_ANY_HIT | RT_QUERY_SORT;
+
+// What every query entry point checks before it takes the scene's lock.
+int query_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, const double* normals) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (flags & ~kQueryFlags) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags & ~kQueryFlags);
+  if ((flags & RT_QUERY_ANY_HIT) && normals)
+    return fail(RT_E_INVALID, "normals are not available with RT_QUERY_ANY_HIT");
+  if (n > 0 && !hits) return fail(RT_E_INVALID, "null hits");
+  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
+  return RT_OK;
+}
+
+int pick_check(const rt_options* o) {
+  if (!o) return fail(RT_E_INVALID, "null options");
+  if (o->width <= 0 || o->height <= 0 || o->width > 65536 || o->height > 65536)
+    return fail(RT_E_INVALID, "bad image size %dx%d", o->width, o->height);
+  if (o->precision != RT_FP64)
+    return fail(o->precision == RT_FP32 ? RT_E_UNSUPPORTED : RT_E_INVALID, "ray queries are float64 only (precision %d)",
+                o->precision);
+  return RT_OK;
+}
+
+// RenderParams<double> as the float64 render fills it, without a
+// framebuffer, pixel records or lists: the scene, and for picks the camera
+// and the image size castPrimaryRay reads (fill_params' operations).
+void fill_query(const rt_scene* s, int width, int height, RenderParams<double>& p) {
+  std::memset(&p, 0, sizeof p);
+  p.objects = s->f64.objects.p;
+  p.lights = s->f64.lights.p;
+  p.meshes = s->f64.meshes.p;
+  p.nodes = s->nodes.p;
+  p.tris = s->f64.tris.p;
+  p.normals = s->f64.normals.p;
+  for (int k = 0; k < 16; ++k) p.c2w[k] = s->c2w[k];
+  for (int k = 0; k < 3; ++k) p.bg[k] = s->bg[k];
+  p.f = std::tan(s->fov * (3.14159265358979323846 / 180.0) / 2);
+  p.aspect = (double)width / (double)height;
+  p.inv_len = 1.0;
+  p.nobj = s->nobj;
+  p.nlight = s->nlight;
+  p.width = width;
+  p.height = height;
+  p.grid_m = 1;
+  p.spp = 1;
+  p.shadow_mesh = s->shadow_mesh;
+  p.lean_plane = -1;
+  p.max_iters = (int32_t)std::min<int64_t>(INT32_MAX, 2 * s->num_nodes + 16);
+}
+
+// The device body of every query (the scene's lock held, its device
+// current): q's ray, hit and normal pointers are device memory.
+int query_device(rt_scene* s, const RenderParams<double>& p, QueryParams q, uint32_t flags, hipStream_t st,
+                 rt_stats* out) {
+  if (!s->q_done) HIP_TRY(hipEventCreateWithFlags(&s->q_done.h, hipEventDisableTiming));
+  // after a render still in flight on the scene, and after the last query
+  // (it shares this one's temporaries) unless this stream orders them anyway
+  if (st != s->done_stream) HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
+  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
+  const size_t rows = (size_t)s->max_waves;
+  if (s->q_partials.n < (rows + 1) * kStatSlots) {
+    if (int rc = s->q_partials.alloc((rows + 1) * kStatSlots)) return rc;
+  }
+  if (s->q_blocks_per_cu < 0) s->q_blocks_per_cu = rtmi_query_blocks_per_cu();
+  if (s->q_blocks_per_cu <= 0) return fail(RT_E_DEVICE, "the ray query kernel is not resident on this device");
+  q.any_hit = (flags & RT_QUERY_ANY_HIT) ? 1 : 0;
+  q.partials = s->q_partials.p;
+  q.order = nullptr;
+  if (flags & RT_QUERY_SORT) {
+    const size_t need = rtmi_query_sort_bytes(q.n);
+    if (!need) return fail(RT_E_DEVICE, "sizing the ray sort failed");
+    if (s->q_sort.n < need) {
+      // an earlier query may still read the old buffer
+      if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+      if (int rc = s->q_sort.alloc(need)) return rc;
+    }
+    QuerySortBufs b;
+    rtmi_query_sort_carve(s->q_sort.p, q.n, &b);
+    if (const int e = rtmi_query_sort(&q, &b, st))
+      return fail(RT_E_DEVICE, "ray sort failed: %s", hipGetErrorString((hipError_t)e));
+    q.order = b.idx2;
+  }
+  // the grid: the device's resident blocks, or fewer when the batch is small
+  const long long steps = (q.n + 63) / 64;
+  const int blocks = (int)std::max(1LL, std::min({(steps + 3) / 4, (long long)s->q_blocks_per_cu * s->num_cus,
+                                                  (long long)s->max_waves / 4}));
+  if (const int e = rtmi_launch_query(&p, &q, blocks, st))
+    return fail(RT_E_DEVICE, "ray query launch failed: %s", hipGetErrorString((hipError_t)e));
+  unsigned long long* acc = s->q_partials.p + rows * kStatSlots;
+  if (out) {
+    if (const int e = rtmi_launch_query_reduce(s->q_partials.p, blocks * 4, acc, st))
+      return fail(RT_E_DEVICE, "ray query stats reduction failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  HIP_TRY(hipEventRecord(s->q_done, st));
+  s->q_done_rec = true;
+  s->q_stream = st;
+  if (out) {
+    unsigned long long h[kStatSlots];
+    HIP_TRY(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = rt_stats{};
+    out->num_primary_rays = q.xy ? h[STAT_PRIMARY] : 0;  // camera rays are a pick's; the kernel counts the rays it traced
+    out->num_intersection_tests = h[STAT_TESTS];
+    out->num_intersection_hits = h[STAT_HITS];
+  }
+  return RT_OK;
+}
+
+// Host form: the batch copied into the scene's staging buffer, queried on
+// the scene's own stream, the answers copied back. in[k]: host arrays of
+// in_bytes[k] bytes (nullptr: absent).
+int query_host(rt_scene* s, const RenderParams<double>& p, int64_t n, const void* const in[4], const size_t in_bytes[4],
+               uint32_t flags, rt_hit* hits, double* normals, rt_stats* out) {
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  size_t off[6], total = 0;
+  for (int k = 0; k < 4; ++k) {
+    off[k] = total;
+    total += in[k] ? al(in_bytes[k]) : 0;
+  }
+  off[4] = total;
+  total += al((size_t)n * sizeof(rt_hit));
+  off[5] = total;
+  total += normals ? al((size_t)n * 3 * sizeof(double)) : 0;
+  hipStream_t st = s->stream;
+  if (s->q_stage.n < total) {
+    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+    if (int rc = s->q_stage.alloc(total)) return rc;
+  }
+  unsigned char* base = s->q_stage.p;
+  // the staging buffer's last user was a query on this stream, or has been waited for
+  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
+  for (int k = 0; k < 4; ++k)
+    if (in[k]) HIP_TRY(hipMemcpyAsync(base + off[k], in[k], in_bytes[k], hipMemcpyHostToDevice, st));
+  QueryParams q{};
+  q.orig = in[0] ? (const double*)(base + off[0]) : nullptr;
+  q.dir = in[1] ? (const double*)(base + off[1]) : nullptr;
+  q.tnear = in[2] ? (const double*)(base + off[2]) : nullptr;
+  q.xy = in[3] ? (const double*)(base + off[3]) : nullptr;
+  q.hits = (QueryHit*)(base + off[4]);
+  q.normals = normals ? (double*)(base + off[5]) : nullptr;
+  q.n = n;
+  if (int rc = query_device(s, p, q, flags, st, out)) return rc;
+  HIP_TRY(hipMemcpyAsync(hits, base + off[4], (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+  if (normals)
+    HIP_TRY(hipMemcpyAsync(normals, base + off[5], (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return RT_OK;
+}
+
+}  // namespace
+
+static_assert(sizeof(rt_hit) == sizeof(QueryHit), "rt_hit layout");
+
+extern "C" int rt_trace_rays_device(rt_scene* s, int64_t n, const double* d_orig, const double* d_dir,
+                                    const double* d_tnear, uint32_t flags, rt_hit* d_hits, double* d_normals,
+                                    void* stream, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  RenderParams<double> p;
+  fill_query(s, 1, 1, p);
+  QueryParams q{};
+  q.orig = d_orig;
+  q.dir = d_dir;
+  q.tnear = d_tnear;
+  q.hits = (QueryHit*)d_hits;
+  q.normals = d_normals;
+  q.n = n;
+  return query_device(s, p, q, flags, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_trace_rays(rt_scene* s, int64_t n, const double* orig, const double* dir, const double* tnear,
+                             uint32_t flags, rt_hit* hits, double* normals, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
+  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  RenderParams<double> p;
+  fill_query(s, 1, 1, p);
+  const size_t v3 = (size_t)n * 3 * sizeof(double);
+  const void* const in[4] = {orig, dir, tnear, nullptr};
+  const size_t bytes[4] = {v3, v3, (size_t)n * sizeof(double), 0};
+  return query_host(s, p, n, in, bytes, flags, hits, normals, out);
+}
+
+extern "C" int rt_pick_pixels_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_xy, uint32_t flags,
+                                     rt_hit* d_hits, double* d_normals, void* stream, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (int rc = pick_check(o)) return rc;
+  if (n > 0 && !d_xy) return fail(RT_E_INVALID, "null pixel positions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  RenderParams<double> p;
+  fill_query(s, o->width, o->height, p);
+  QueryParams q{};
+  q.xy = d_xy;
+  q.hits = (QueryHit*)d_hits;
+  q.normals = d_normals;
+  q.n = n;
+  return query_device(s, p, q, flags, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_pick_pixels(rt_scene* s, const rt_options* o, int64_t n, const double* xy, uint32_t flags,
+                              rt_hit* hits, double* normals, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
+  if (int rc = pick_check(o)) return rc;
+  if (n > 0 && !xy) return fail(RT_E_INVALID, "null pixel positions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  RenderParams<double> p;
+  fill_query(s, o->width, o->height, p);
+  const void* const in[4] = {nullptr, nullptr, nullptr, xy};
+  const size_t bytes[4] = {0, 0, 0, (size_t)n * 2 * sizeof(double)};
+  return query_host(s, p, n, in, bytes, flags, hits, normals, out);
+}

@@ -1,5 +1,5 @@
 // rt_query.h — ray queries (include/rtmi.h rt_trace_rays* / rt_pick_pixels*):
-// what the host library (rtmi.cpp) and the query kernels
+// what the host library (rt_queries.cpp) and the query kernels
 // (rt_kernels_query.hip) share.
 #pragma once
 #include <stddef.h>

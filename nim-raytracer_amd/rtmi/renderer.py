@@ -220,7 +220,7 @@ class DeviceScene:
 
     def last_pipelined(self):
         """Whether the last render call was pipelined (its build on the
-        scene's build stream, its own buffer set: rtmi.cpp rt_scene::pipe) —
+        scene's build stream, its own buffer set: rt_scene.h rt_scene::pipe) —
         such calls on two alternating streams may render at once."""
         f = lib().rtmi_test_last_pipelined
         f.restype = C.c_int

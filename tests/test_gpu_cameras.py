@@ -1,4 +1,4 @@
-"""The per-call device builders (csrc/rt_frame.hip, rtmi.cpp frame_build /
+"""The per-call device builders (csrc/rt_frame.hip, rt_render.cpp frame_build /
 frame_obj_masks) under cameras other than the standard viewpoint
 (tests/cameras.py): a mesh a hair in front of the camera plane, views along,
 across, from below and from exactly on the ground plane, a mesh a few pixels

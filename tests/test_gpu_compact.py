@@ -87,6 +87,29 @@ def test_compact_rows_and_bands_match_full_frame(gpu, name):
         assert torch.equal(fb, full), (world, band_h)
 
 
+def test_compact_buffers_are_counted_and_freed(gpu):
+    """The buffers a compacted render allocates on demand (k_render_wave's
+    queues and the per-pixel secondary sums, 3 x 8 bytes per pixel: 2.25 MiB
+    here) are part of device_bytes and go back to the device with the scene."""
+    import torch
+    w, h = 384, 256
+    o = _opts(w, h, 1, RT_FLAG_COMPACT)
+    fb = torch.zeros(w * h * 3, dtype=torch.float32, device="cuda")
+    # once through, so that the kernels' code and the runtime's own pools are resident
+    ds = DeviceScene(scenes.SCENES["spheres-reflection"]())
+    ds.render_device(o, fb)
+    ds.close()
+    torch.cuda.synchronize()
+    start = torch.cuda.mem_get_info()[0]
+    ds = DeviceScene(scenes.SCENES["spheres-reflection"]())
+    before = ds.info()["device_bytes"]
+    ds.render_device(o, fb)
+    assert ds.last_compacted()
+    assert ds.info()["device_bytes"] - before >= w * h * 3 * 8
+    ds.close()
+    assert torch.cuda.mem_get_info()[0] == start
+
+
 def _check(got, ref, what, frac=0.995, tol=2e-3, mean_tol=2e-4):
     err = np.abs(got.astype(np.float64) - ref.astype(np.float64)).max(axis=-1)
     ok = float((err <= tol).mean())

@@ -222,7 +222,7 @@ def test_list_past_its_slots_takes_the_bvh(gpu, lg):
 
 
 def test_4k_frames_get_128_slots(gpu):
-    """4K frames get 128 list slots per pixel (rtmi.cpp slot_lg_for; 1080p
+    """4K frames get 128 list slots per pixel (rt_scene.h slot_lg_for; 1080p
     keeps 64): the C5 torus's fullest pixels (up to 99 camera-ray faces at
     4K, around row 1184) then stay in the batched kernel instead of taking the
     one-sample BVH loop at ~100x a pixel's cost, and the rows render the same

@@ -170,7 +170,7 @@ def test_forced_fallback(gpu):
 
 
 # (bias, lights or None for the scene's two): the per-call condition of the
-# uniform-lit proof (rtmi.cpp uniform_cam) fails, so nothing may be tagged
+# uniform-lit proof (rt_render.cpp uniform_cam) fails, so nothing may be tagged
 NOT_LIT = [
     (0.0, None),
     (1e-7, None),                          # bias below the rounding error of the shadow origin's height

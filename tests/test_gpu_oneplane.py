@@ -1,5 +1,5 @@
 """The one-plane float32 kernels (k_render_mix1 / _gen1 / _lean1q) away from
-the ground at y = 0, on the thresholds of their per-call proofs (rtmi.cpp
+the ground at y = 0, on the thresholds of their per-call proofs (rt_render.cpp
 uniform_cam, rt_bins_geom.h uniform_class, the ground tag of k_frame_lists,
 rt_fast.h lean1q_loop's constant sum and ground1_batch) and across a seeded
 population of cameras (cameras.oneplane_case).

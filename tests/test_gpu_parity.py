@@ -177,7 +177,7 @@ def test_bands_and_unshard_match_full_frame(gpu):
 
 
 def test_launch_order_does_not_change_results(gpu):
-    """The float32 work queue's expensive-first order (rtmi.cpp group_order:
+    """The float32 work queue's expensive-first order (rt_render.cpp group_order:
     the first launch of a mapping measures per-group costs, later ones hand
     groups out longest-first) is scheduling only: frames and Stats are
     bit-identical to screen order (RT_FLAG_NO_REORDER), whole frame and

@@ -1,4 +1,4 @@
-"""Pipelined per-call builds (rtmi.cpp rt_scene::pipe): a float32 call that
+"""Pipelined per-call builds (rt_scene.h rt_scene::pipe): a float32 call that
 renders at most a third of the image (a multi-GPU rank's bands, a pool's
 scanlines) builds its camera-dependent data on the scene's build stream into
 the other of two buffer sets, overlapping the previous call's render. Calls

@@ -1,4 +1,4 @@
-"""Two-class launches of the float32 kernel (rtmi.cpp split_lists): lean
+"""Two-class launches of the float32 kernel (rt_render.cpp launch): lean
 pixels — no camera ray can hit the mesh, every light is a distant light whose
 shadow rays provably miss it — render in k_render_lean from a per-launch
 list (k_render_lean1 in one-plane scenes, RT_FLAG_NO_LEAN1 turns it off), the rest in
@@ -31,7 +31,7 @@ FLAG_SETS = (0, RT_FLAG_NO_MIX, RT_FLAG_NO_LEAN1, RT_FLAG_NO_GEN1, RT_FLAG_NO_BA
 def _opts(w, h, m, flags=0, aa=akGrid, bias=1e-4, seed=0):
     # NO_REORDER: a short launch (these small frames) otherwise hands its
     # groups out longest-first from a measuring launch, and such launches
-    # keep the one kernel (rtmi.cpp split_lists) — the split would go untested
+    # keep the one kernel (rt_render.cpp launch) — the split would go untested
     return Options(width=w, height=h, antialias=Antialias(aa, m), bias=bias, precision=Precision.fp32,
                    flags=flags | RT_FLAG_NO_REORDER, seed=seed)
 
@@ -193,8 +193,8 @@ def test_lean1_kernel_choice(gpu, m):
 ])
 def test_lean1_light_sides(gpu, dirs):
     """k_render_lean1q / _mix1 test a lit sample's shadow rays against the
-    plane once when every light is on the same side of it (or none off it,
-    rtmi.cpp lights_one_side), per light otherwise: both equal the general
+    plane once when every light is on the same side of it (or none off it),
+    per light otherwise: both equal the general
     kernels, frames and Stats."""
     import torch
     from rtmi.glm import normalize, vec
@@ -269,7 +269,7 @@ def test_batched_general_pixels_and_fallback(gpu):
 def test_split_in_band_launches(gpu):
     """A multi-GPU rank's band set is a short launch: every launch — the
     first included, nothing is measured on an earlier frame (launch orders
-    from measured costs are off by default, rtmi.cpp order_policy) — builds
+    from measured costs are off by default, rt_render.cpp order_policy) — builds
     its own lean and general lists on the device and renders them. Same
     frames and Stats as the one-kernel launch."""
     import torch

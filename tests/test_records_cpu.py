@@ -1,4 +1,4 @@
-"""The per-light shadow-test records (rt_common.h LTri, rtmi.cpp make_ltri)
+"""The per-light shadow-test records (rt_common.h LTri, rt_bins_geom.h make_ltri)
 against the reference's Moller-Trumbore test (geom.nim:283-336, the oracle's
 float64 restatement): evaluated as the kernels do — three float32 FMA chains
 and min(u, v, 1 - (u + v)) >= 0 — a record gives the oracle's verdict on

@@ -1,4 +1,4 @@
-"""The uniform-pixel proof (rt_bins_geom.h uniform_class, rtmi.cpp
+"""The uniform-pixel proof (rt_bins_geom.h uniform_class, rt_render.cpp
 uniform_cam) against every sample it speaks about, on the host: the class of
 a pixel is a claim about all m x m samples of lean1q_loop's float32
 arithmetic, which the GPU frames sample at a few thousand pixels and this file
@@ -6,7 +6,7 @@ checks at every pixel of a 64 x 40 frame for 200 seeded cameras (the
 population of test_gpu_oneplane.py, cameras.oneplane_case) and m = 16, 32, 64:
 about 2 x 10^9 samples.
 
-The hooks (rtmi.cpp rtmi_test_uniform, rtmi_test_uniform_samples) form
+The hooks (rt_hooks.cpp rtmi_test_uniform, rtmi_test_uniform_samples) form
 FastParams and UniformCam through the functions a render call uses and
 evaluate the kernel's cx, cy and N per sample with fmaf on the host; the
 claims are checked here in numpy:

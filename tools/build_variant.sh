@@ -19,8 +19,10 @@ for k in $(seq 0 15); do
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off $2 -c csrc/rt_frame.hip -o build/var/$1/frame.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off $2 -c csrc/rt_kernels_f64.hip -o build/var/$1/f64.o &
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -ffp-contract=off $2 -c csrc/rtmi.cpp -o build/var/$1/rtmi.o &
+for u in rtmi rt_scene_lights rt_scene_mesh rt_render rt_queries rt_hooks; do  # the host units of the C-ABI
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -ffp-contract=off $2 -c csrc/$u.cpp -o build/var/$1/$u.o &
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -ffp-contract=off $2 -c csrc/rt_bins.cpp -o build/var/$1/bins.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -ffp-contract=off $2 -c csrc/rt_bvh_gpu.hip -o build/var/$1/bvh_gpu.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../tools/ab/$1.so build/var/$1/main.o build/var/$1/part*.o build/var/$1/f64.o build/rt_kernels_io.o build/var/$1/rtmi.o build/rt_bvh.o build/var/$1/bvh_gpu.o build/rt_queue.o build/rt_obj.o build/rt_multi.o build/var/$1/bins.o build/var/$1/frame.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../tools/ab/$1.so build/var/$1/main.o build/var/$1/part*.o build/var/$1/f64.o build/rt_kernels_io.o build/rt_kernels_query.o build/rt_lights_gpu.o build/rt_mesh_gpu.o build/var/$1/rtmi.o build/var/$1/rt_scene_lights.o build/var/$1/rt_scene_mesh.o build/var/$1/rt_render.o build/var/$1/rt_queries.o build/var/$1/rt_hooks.o build/rt_bvh.o build/var/$1/bvh_gpu.o build/rt_queue.o build/rt_obj.o build/rt_multi.o build/var/$1/bins.o build/var/$1/frame.o
