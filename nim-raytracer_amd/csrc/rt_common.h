@@ -380,7 +380,7 @@ struct alignas(16) LTri {
 static_assert(sizeof(LTri) == 64, "LTri must be 64 bytes (one scalar load, TriFast-sized offsets)");
 // reflection queue of a k_render_wave wave: up to 63 rays left over plus a
 // pass's 64 new ones; fields ro xyz, rd xyz, weight, dst * 16 + depth
-constexpr int kReflQueue = 128, kReflFields = 8;
+constexpr int kReflQueue = 128, kReflFields = 9;
 
 enum : int32_t {
   STAT_PRIMARY = 0, STAT_TESTS = 1, STAT_HITS = 2, STAT_SHADOW = 3, STAT_REFL = 4,

@@ -716,11 +716,10 @@ __device__ __forceinline__ V3<R> object_normal(const RT_CONST DevObject<R>& ob, 
     const V3<R> c{(vmin.x + vmax.x) * R(0.5), (vmin.y + vmax.y) * R(0.5), (vmin.z + vmax.z) * R(0.5)};
     const V3<R> pp{ho.x - c.x, ho.y - c.y, ho.z - c.z};
     const V3<R> dd{(vmin.x - vmax.x) * R(0.5), (vmin.y - vmax.y) * R(0.5), (vmin.z - vmax.z) * R(0.5)};
-    // float64: the reference's 1.000001 verbatim. float32: the hit point is
-    // only good to ~1e-5 of the box size, so 1.000001 can truncate every
-    // axis to 0 (a NaN normal); widen to 1.0001 and fall back to the
-    // dominant axis.
-    const R bias = Prec<R>::exact ? R(1.000001) : R(1.0001);
+    // The reference's 1.000001 verbatim. float32: the hit point is only good
+    // to ~1e-6 of the box size, so every axis can truncate to 0 (a NaN
+    // normal): fall back to the dominant axis (rt_fast.h analytic_normal).
+    const R bias = R(1.000001);
     const R qx = Prec<R>::div(pp.x, fabs(dd.x)), qy = Prec<R>::div(pp.y, fabs(dd.y)),
             qz = Prec<R>::div(pp.z, fabs(dd.z));
     V3<R> n{R((long long)(qx * bias)), R((long long)(qy * bias)), R((long long)(qz * bias))};

@@ -652,9 +652,17 @@ __device__ __forceinline__ unsigned long long mesh_search(KP p, const FObj& ob, 
 }
 
 
+// src (per lane; reflected rays): the plane the ray was reflected off, -1
+// for every other ray. Such a ray starts at hit + r * bias and runs along r,
+// so it meets that plane at t = -bias exactly: a miss, whatever the plane's
+// transform. Recomputed from the float32 hit point, whose distance to the
+// plane is rounding error (up to an ulp of the camera's height, more under a
+// general transform), t comes out positive where |r . n| * bias is smaller
+// than that error (the ground towards the horizon); the lane takes the exact
+// answer instead.
 template <bool COUNT, unsigned F>
 __device__ __forceinline__ Hit trace(KP p, F3 o, F3 d, float tmax, bool active, bool shadow, int pix, int light,
-                                     Stats32& ws, bool no_mesh = false) {
+                                     Stats32& ws, bool no_mesh = false, int src = -1) {
   RT_STAMP(t_trace0);
   Hit h{-1, -1, tmax};
   const bool early = (F & F_MESH) && shadow && p->shadow_mesh >= 0;
@@ -765,6 +773,7 @@ __device__ __forceinline__ Hit trace(KP p, F3 o, F3 d, float tmax, bool active, 
         tri = best;
       }
     }
+    if ((F & F_REFLECT) && i == src) t = -finf();
 #if RTMI_FCMP_MASKS
     const unsigned long long um = m_ge(t, 0.0f) & m_lt(t, h.t) & actm;
     ws.v[STAT_HITS] += pc(um);
@@ -810,9 +819,13 @@ __device__ __forceinline__ F3 analytic_normal(const FObj& ob, F3 ho) {
     const float qx = (ho.x - cx) * rcp(fabsf((ob.lo[0] - ob.hi[0]) * 0.5f));
     const float qy = (ho.y - cy) * rcp(fabsf((ob.lo[1] - ob.hi[1]) * 0.5f));
     const float qz = (ho.z - cz) * rcp(fabsf((ob.lo[2] - ob.hi[2]) * 0.5f));
-    // 1.0001 instead of 1.000001: a float32 hit point is good to ~1e-5 of
-    // the box size; fall back to the dominant axis rather than a NaN normal.
-    F3 n = f3(truncf(qx * 1.0001f), truncf(qy * 1.0001f), truncf(qz * 1.0001f));
+    // The reference's 1.000001: an axis counts within 1e-6 of its face, so
+    // only there (an edge, a corner) is the normal diagonal. A float32 hit
+    // point is good to ~1e-6 of the box size and may truncate every axis to
+    // 0: then the dominant axis, rather than a NaN normal. (A wider factor
+    // instead, 1.0001, made the normal diagonal, and the face unlit, within
+    // 1e-4 of every edge: a band a hundred times the reference's.)
+    F3 n = f3(truncf(qx * 1.000001f), truncf(qy * 1.000001f), truncf(qz * 1.000001f));
     if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) {
       const float ax = fabsf(qx), ay = fabsf(qy), az = fabsf(qz);
       if (ax >= ay && ax >= az) n.x = qx < 0.0f ? -1.0f : 1.0f;
@@ -830,7 +843,13 @@ __device__ __forceinline__ F3 analytic_normal(const FObj& ob, F3 ho) {
 // conflicts). Parking the reflected ray and the hit point here instead of in
 // VGPRs takes them out of the register peak, which sits inside the
 // shadow-ray traversal (DESIGN.md "Occupancy").
-enum : int { LDS_RO = 0, LDS_RD = 3, LDS_HW = 6, LDS_ALB = 9, kLdsSlots = 12 };
+enum : int { LDS_RO = 0, LDS_RD = 3, LDS_HW = 6, LDS_ALB = 9, kLdsSlots = 12, LDS_SRC = 12 };
+// LDS_SRC (reflective kernels only: one slot more): the plane a parked
+// reflected ray left, -1 when it left another kind of object (trace's `src`).
+template <unsigned F>
+constexpr int lds_slots() {
+  return (F & F_REFLECT) ? kLdsSlots + 1 : kLdsSlots;
+}
 // An LDS-typed pointer: 32-bit addresses with the slot offsets folded into
 // the ds_* immediates (a generic float* here became a 64-bit flat address
 // per slot, hoisted and pinned in VGPRs).
@@ -880,6 +899,14 @@ __device__ __forceinline__ F3 lds_get3(LdsF* ls, int slot) {
   volatile LdsF* q = ls;
   return f3(q[(slot + 0) * 64], q[(slot + 1) * 64], q[(slot + 2) * 64]);
 }
+__device__ __forceinline__ void lds_put1(LdsF* ls, int slot, float v) {
+  volatile LdsF* q = ls;
+  q[slot * 64] = v;
+}
+__device__ __forceinline__ float lds_get1(LdsF* ls, int slot) {
+  volatile LdsF* q = ls;
+  return q[slot * 64];
+}
 
 // One shading level of renderer.nim's shade (renderer.nim:71-127 at one
 // recursion depth) for the wave's `act` lanes, at forward weight w:
@@ -895,19 +922,21 @@ __device__ __forceinline__ F3 lds_get3(LdsF* ls, int slot) {
 // pix: the sample's pixel index (y * width + x) for the camera ray's bins;
 // pinfo: the wave's pixel record (FastParams.pix_info) when the wave holds
 // one pixel, else kPixCount (nothing known).
+// src: trace's src of this level's ray; the parked ray's is left at LDS_SRC.
 template <bool COUNT, unsigned F, bool LEAN = false>
 __device__ __forceinline__ void shade_level(KP& p, F3 o, F3 d, bool act, int lev, int depth, float w, int pix,
                                             unsigned pinfo, LdsF* ls, F3& v, bool& reflect, float& refl_out,
-                                            Stats32& ws) {
+                                            Stats32& ws, int src = -1) {
   v = f3(0.0f, 0.0f, 0.0f);
   const Hit hit = trace<COUNT, F>(p, o, d, finf(), act, false, lev == 0 ? pix : -1, -1, ws,
-                                  lev == 0 && (LEAN || (pinfo & kPixCount) == 0u));
+                                  lev == 0 && (LEAN || (pinfo & kPixCount) == 0u), src);
   if (act && hit.obj < 0) v = f3(mul_nc(w, p->bg[0]), mul_nc(w, p->bg[1]), mul_nc(w, p->bg[2]));
   const bool lit = act && hit.obj >= 0;
   const F3 hw = f3(__builtin_fmaf(d.x, hit.t, o.x), __builtin_fmaf(d.y, hit.t, o.y), __builtin_fmaf(d.z, hit.t, o.z));
   F3 N = f3(0.0f, 0.0f, 0.0f);
   F3 alb = f3(0.0f, 0.0f, 0.0f);
   float refl = 0.0f;
+  int plane_hit = -1;
   unsigned long long pending = bal(lit);
   while (pending) {  // one pass per distinct object hit by the wave
     const int lead = (int)__builtin_ctzll(pending);
@@ -945,6 +974,7 @@ __device__ __forceinline__ void shade_level(KP& p, F3 o, F3 d, bool act, int lev
       }
       alb = oalb;
       refl = orefl;
+      if ((F & F_REFLECT) && ob.type == GEOM_PLANE) plane_hit = oi;
     }
   }
   reflect = (F & F_REFLECT) && lit && refl > 0.0f && depth <= p->max_depth;
@@ -963,6 +993,7 @@ __device__ __forceinline__ void shade_level(KP& p, F3 o, F3 d, bool act, int lev
       lds_put3(ls, LDS_RO, f3(__builtin_fmaf(rd.x, p->bias, hw.x), __builtin_fmaf(rd.y, p->bias, hw.y),
                               __builtin_fmaf(rd.z, p->bias, hw.z)));
       lds_put3(ls, LDS_RD, rd);
+      lds_put1(ls, LDS_SRC, __int_as_float(plane_hit));
     }
   }
   const F3 so = f3(__builtin_fmaf(N.x, p->bias, hw.x), __builtin_fmaf(N.y, p->bias, hw.y),
@@ -1017,6 +1048,7 @@ __device__ __forceinline__ void shade_path(KP p, F3 o, F3 d, bool active, int pi
                                            Acc& acc, Stats32& ws) {
   bool act = active;
   int depth = 1;
+  int src = -1;
   float w = 1.0f;
   for (int lev = 0; lev < ((F & F_REFLECT) ? kMaxShadeLevels : 1); ++lev) {
     if (LEAN == 0) p = params();
@@ -1024,13 +1056,14 @@ __device__ __forceinline__ void shade_path(KP p, F3 o, F3 d, bool active, int pi
     F3 v;
     bool reflect;
     float refl;
-    shade_level<COUNT, F, LEAN>(p, o, d, act, lev, depth, w, pix, pinfo, ls, v, reflect, refl, ws);
+    shade_level<COUNT, F, LEAN>(p, o, d, act, lev, depth, w, pix, pinfo, ls, v, reflect, refl, ws, src);
     if (act) acc_add3(acc, v.x, v.y, v.z);
     // every lane reloads (lanes that do not reflect go inactive): o and d
     // are then dead across the light loop instead of carried for them
     if ((F & F_REFLECT) && bal(reflect)) {
       o = lds_get3(ls, LDS_RO);
       d = lds_get3(ls, LDS_RD);
+      src = reflect ? __float_as_int(lds_get1(ls, LDS_SRC)) : -1;
     }
     w = w * refl;
     ++depth;
@@ -2821,7 +2854,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUNT ? 4u 
 k_render_fast(const FastParams params_by_value) {
   (void)params_by_value;  // read through params() (kernarg segment)
   KP p = params();
-  __shared__ float lds[4][kLdsSlots][64];            // 4 waves per 256-thread block
+  __shared__ float lds[4][lds_slots<F>()][64];       // 4 waves per 256-thread block
   extern __shared__ float sample_lds[];              // (multi-)jittered tables, sized by the host
   __shared__ unsigned long long lds_tot[4][kStatSlots];  // per-wave 64-bit Stats totals
   const int wib = (int)(threadIdx.x >> 6);
@@ -3063,7 +3096,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wave_waves<
   static_assert(F & F_REFLECT, "the compacting kernel serves reflective scenes");
   (void)params_by_value;
   KP p = params();
-  __shared__ float lds[4][kLdsSlots][64];
+  __shared__ float lds[4][lds_slots<F>()][64];
   extern __shared__ float sample_lds[];
   __shared__ unsigned long long lds_tot[4][kStatSlots];
   const int wib = (int)(threadIdx.x >> 6);
@@ -3129,7 +3162,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wave_waves<
     F3 o, d;
     bool act;
     float w;
-    int depth, dst, lev;
+    int depth, dst, lev, src = -1;
     if (from_q) {  // a pass over the newest min(qn, 64) queued rays
       const int n = min(qn, 64);
       qn -= n;
@@ -3142,6 +3175,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wave_waves<
       const int meta = __float_as_int(rq_load(e + 7 * kReflQueue));
       dst = meta >> 4;
       depth = meta & 15;
+      src = __float_as_int(rq_load(e + 8 * kReflQueue));
       lev = 1;
     } else {  // the item's next camera iteration: level 0 of its samples
       const int s = it * p->lanes_per_px + gp.sub;
@@ -3159,7 +3193,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wave_waves<
     bool reflect;
     float refl;
     shade_level<false, F, false>(p, o, d, act, lev, depth, w, lev == 0 && act ? gp.y * p->width + gp.x : -1, pinfo,
-                                 ls, v, reflect, refl, ws);
+                                 ls, v, reflect, refl, ws, act ? src : -1);
     p = params();
     if (lev == 0) {
       if (act) acc_add3(pacc, v.x, v.y, v.z);
@@ -3180,6 +3214,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wave_waves<
         e[5 * kReflQueue] = rd.z;
         e[6 * kReflQueue] = w * refl;
         e[7 * kReflQueue] = __int_as_float(dst * 16 + depth + 1);
+        e[8 * kReflQueue] = lds_get1(ls, LDS_SRC);
       }
       qn += (int)pc(rm);
     }

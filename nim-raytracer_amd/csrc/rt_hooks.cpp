@@ -56,6 +56,14 @@ extern "C" int64_t rtmi_test_frame_lists(rt_scene* s, int32_t* off, int32_t* ent
   return std::min<int64_t>(n, ent_cap);
 }
 
+// The float32 kernel specialisation (SUB_* bits, rt_common.h) a render call
+// with these options launches on this scene: f32_subset, as the launch reads it.
+extern "C" int rtmi_test_f32_subset(rt_scene* s, const rt_options* o) {
+  if (!s || !o) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  return (int)f32_subset(s, o);
+}
+
 // Test hook: the LTri record (rt_common.h) of triangle v9 (v0, v1, v2 as 9
 // doubles, mesh object space) for the shadow direction d (float64), as
 // rt_scene_create builds it; out: 16 words.

@@ -71,6 +71,12 @@ void fast_camera(const double* c2w, double fov, const rt_options* o, FastParams&
   p.spp = spp;
 }
 
+// The float32 kernel specialisation of a launch: the scene's features plus
+// stochastic sampling when the options ask for it.
+unsigned f32_subset(const rt_scene* s, const rt_options* o) {
+  return s->f32_subset | (o->aa_kind >= RT_AA_JITTERED ? SUB_STOCHASTIC : 0u);
+}
+
 }  // namespace rtmi
 
 namespace {
@@ -95,12 +101,6 @@ int check_options(const rt_scene* s, const rt_options* o) {
     return fail(RT_E_UNSUPPORTED, "max_ray_depth %d > %d with reflective materials", o->max_ray_depth,
                 kMaxShadeLevels - 1);
   return RT_OK;
-}
-
-// The float32 kernel specialisation of a launch: the scene's features plus
-// stochastic sampling when the options ask for it.
-unsigned f32_subset(const rt_scene* s, const rt_options* o) {
-  return s->f32_subset | (o->aa_kind >= RT_AA_JITTERED ? SUB_STOCHASTIC : 0u);
 }
 
 // Lanes per pixel of a float32 launch (a power of two, <= 64): as many as

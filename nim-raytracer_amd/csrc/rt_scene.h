@@ -366,5 +366,6 @@ void refresh_host_lists(rt_scene* s);
 // rt_render.cpp
 void uniform_cam(float ty, const float* light_vy, const FastParams& p, bg::UniformCam& u);
 void fast_camera(const double* c2w, double fov, const rt_options* o, FastParams& p);
+unsigned f32_subset(const rt_scene* s, const rt_options* o);
 
 }  // namespace rtmi

@@ -231,6 +231,20 @@ class DeviceScene:
             raise RuntimeError("rtmi_test_last_pipelined failed")
         return bool(r)
 
+    def f32_subset(self, opts: Options):
+        """The float32 kernel specialisation a render call with `opts`
+        launches on this scene: the SUB_* feature bits (csrc/rt_common.h:
+        sphere 1, box 2, mesh 4, general transform 8, point light 16,
+        reflection 32, stochastic sampling 64)."""
+        f = lib().rtmi_test_f32_subset
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(abi.rt_options)]
+        o = opts.to_c()
+        r = f(self.h, C.byref(o))
+        if r < 0:
+            raise RuntimeError("rtmi_test_f32_subset failed")
+        return int(r)
+
     def last_split(self):
         """(lean, general) pixel groups of the last render call (two-class launches)."""
         a, b = C.c_int64(), C.c_int64()
