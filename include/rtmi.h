@@ -358,6 +358,27 @@ int rt_scene_set_mesh_vertices_device(rt_scene *scene, int32_t mesh, const doubl
                                       int64_t num_vertices, const double *d_normals,
                                       void *hip_stream);
 
+/* Replace every object's transform pair, radius, box_min / box_max, albedo and
+ * reflection (Scene.objects' geometry placement and Material): move and
+ * restyle objects in place. num_objects must equal the scene's object count,
+ * each object's type the one given at create and, for RT_MESH, its mesh the
+ * one given at create: RT_E_INVALID otherwise, with the object's index in the
+ * message. Matrices are checked as rt_scene_create checks them (non-affine:
+ * RT_E_UNSUPPORTED).
+ * From the next call on the scene answers exactly as one created by
+ * rt_scene_create from the same description with these objects: frames in
+ * both precisions, Stats, the rt_trace_rays / rt_pick_pixels answers, the
+ * rt_scene_last_* diagnostics and which kernels run are the same, bit for bit.
+ * The meshes (with the vertices of any mesh update), both trees, the triangle
+ * records, normals, lights' descriptions, camera and buffer sets are kept;
+ * the object records, the objects' world boxes and everything that depends on
+ * both the lights and the objects (the light grids over the one mesh object,
+ * the object light grids of 4..64-object scenes, both built on the device)
+ * are formed again. Waits for everything in flight on the scene. On any
+ * failure the scene keeps its previous objects. */
+int rt_scene_set_objects(rt_scene *scene, const rt_object_desc *objects,
+                         int32_t num_objects);
+
 /* ---- rendering ----------------------------------------------------------
  * All render calls implement renderLine (renderer.nim:162-211) for every row
  * y in countup(y0, y1 - 1, step):
@@ -447,6 +468,9 @@ int rt_multi_set_lights(rt_multi *m, const rt_light_desc *lights,
 /* rt_scene_set_mesh_vertices on every rank's scene. */
 int rt_multi_set_mesh_vertices(rt_multi *m, int32_t mesh, const double *vertices,
                                int64_t num_vertices, const double *normals);
+/* rt_scene_set_objects on every rank's scene. */
+int rt_multi_set_objects(rt_multi *m, const rt_object_desc *objects,
+                         int32_t num_objects);
 int rt_multi_destroy(rt_multi *m);
 
 /* ---- render queue (workerpool.nim WorkerPool[WorkMsg, ResponseMsg]) ---- */

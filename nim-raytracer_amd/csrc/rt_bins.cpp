@@ -654,11 +654,24 @@ bool hull_meets_box(const std::vector<std::array<double, 2>>& h, double u0, doub
   return true;
 }
 
-bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3], ObjGridHost* out,
-                             const char** why) {
+namespace {
+
+// What build_object_light_grid forms before its cell loop: the header, the
+// always-set objects, the boxes' growth and every bounded object's projected
+// box and hull. unit: only unbounded objects, a 1x1 grid of off_grid.
+struct ObjGridPrologue {
+  LightGrid g;
+  unsigned long long off_grid = 0;
+  double delta = 0.0;
+  bool unit = false;
+  std::vector<std::array<double, 4>> box;
+  std::vector<std::vector<std::array<double, 2>>> hull;
+};
+
+bool object_grid_prologue(const std::vector<ObjBox>& objs, const double dir[3], ObjGridPrologue* out,
+                          const char** why) {
   *why = "";
   out->g = LightGrid{};
-  out->masks.clear();
   out->off_grid = 0;
   if (objs.size() > 64) {
     *why = "object masks hold at most 64 objects";
@@ -685,9 +698,11 @@ bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3
   for (const ObjBox& b : objs)
     if (!b.always)
       for (int k = 0; k < 3; ++k) scale = std::max(scale, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-  const double delta = 1e-5 * scale;
-  std::vector<std::array<double, 4>> box(objs.size());
-  std::vector<std::vector<std::array<double, 2>>> hull(objs.size());
+  const double delta = out->delta = 1e-5 * scale;
+  std::vector<std::array<double, 4>>& box = out->box;
+  std::vector<std::vector<std::array<double, 2>>>& hull = out->hull;
+  box.assign(objs.size(), std::array<double, 4>{});
+  hull.assign(objs.size(), {});
   double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
   for (size_t i = 0; i < objs.size(); ++i) {
     const ObjBox& b = objs[i];
@@ -725,7 +740,7 @@ bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3
     g.u0 = g.v0 = 0.0f;
     g.inv_h = 1.0f;
     g.gu = g.gv = 1;
-    out->masks.assign(1, out->off_grid);
+    out->unit = true;
     return true;
   }
   const double du = std::max(umax - umin, 1e-30), dv = std::max(vmax - vmin, 1e-30);
@@ -737,14 +752,44 @@ bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3
   g.inv_h = (float)(1.0 / h);
   g.gu = gu;
   g.gv = gv;
+  return true;
+}
+
+// A bounded object's cell rectangle in the grid g (inclusive).
+void object_cell_rect(const LightGrid& g, const std::array<double, 4>& box, int* c0, int* c1, int* r0, int* r1) {
+  const double ih = (double)g.inv_h;
+  *c0 = std::max(0, (int)std::floor((box[0] - (double)g.u0) * ih));
+  *c1 = std::min(g.gu - 1, (int)std::floor((box[1] - (double)g.u0) * ih));
+  *r0 = std::max(0, (int)std::floor((box[2] - (double)g.v0) * ih));
+  *r1 = std::min(g.gv - 1, (int)std::floor((box[3] - (double)g.v0) * ih));
+}
+
+}  // namespace
+
+bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3], ObjGridHost* out,
+                             const char** why) {
+  out->g = LightGrid{};
+  out->masks.clear();
+  out->off_grid = 0;
+  ObjGridPrologue pro;
+  if (!object_grid_prologue(objs, dir, &pro, why)) return false;
+  out->g = pro.g;
+  out->off_grid = pro.off_grid;
+  if (pro.unit) {
+    out->masks.assign(1, out->off_grid);
+    return true;
+  }
+  const LightGrid& g = out->g;
+  const std::vector<std::array<double, 4>>& box = pro.box;
+  const std::vector<std::vector<std::array<double, 2>>>& hull = pro.hull;
+  const double delta = pro.delta;
+  const int gu = g.gu, gv = g.gv;
   const double ih = (double)g.inv_h;
   out->masks.assign((size_t)gu * (size_t)gv, out->off_grid);
   for (size_t i = 0; i < objs.size(); ++i) {
     if (objs[i].always) continue;
-    const int c0 = std::max(0, (int)std::floor((box[i][0] - (double)g.u0) * ih));
-    const int c1 = std::min(gu - 1, (int)std::floor((box[i][1] - (double)g.u0) * ih));
-    const int r0 = std::max(0, (int)std::floor((box[i][2] - (double)g.v0) * ih));
-    const int r1 = std::min(gv - 1, (int)std::floor((box[i][3] - (double)g.v0) * ih));
+    int c0, c1, r0, r1;
+    object_cell_rect(g, box[i], &c0, &c1, &r0, &r1);
     // cells meeting the projected hull of the object box's world corners
     // (grown by delta): a shadow ray can only reach the object through its
     // projection, which the hull of the box's projection contains
@@ -755,6 +800,46 @@ bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3
         if (hull[i].size() < 3 || hull_meets_box(hull[i], cu0, cv0, cu0 + hc + 2 * delta, cv0 + hc + 2 * delta))
           out->masks[(size_t)rr * (size_t)gu + (size_t)cc] |= 1ull << i;
       }
+  }
+  return true;
+}
+
+bool plan_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3], ObjGridPlan* out,
+                            const char** why) {
+  out->rec.clear();
+  ObjGridPrologue pro;
+  if (!object_grid_prologue(objs, dir, &pro, why)) return false;
+  out->g = pro.g;
+  out->off_grid = pro.off_grid;
+  out->delta = pro.delta;
+  if (pro.unit) return true;
+  for (size_t i = 0; i < objs.size(); ++i) {
+    if (objs[i].always) continue;
+    ObjGridRec r;
+    std::memset(&r, 0, sizeof r);
+    object_cell_rect(out->g, pro.box[i], &r.c0, &r.c1, &r.r0, &r.r1);
+    const std::vector<std::array<double, 2>>& h = pro.hull[i];
+    r.nh = (int32_t)h.size();  // at most 8: the hull of 8 projected corners
+    r.obj = (int32_t)i;
+    // hull_meets_box's prologue: the extent, and per edge what does not depend on the cell
+    double pu0 = INFINITY, pu1 = -INFINITY, pv0 = INFINITY, pv1 = -INFINITY;
+    for (const auto& q : h) {
+      pu0 = std::min(pu0, q[0]);
+      pu1 = std::max(pu1, q[0]);
+      pv0 = std::min(pv0, q[1]);
+      pv1 = std::max(pv1, q[1]);
+    }
+    r.pu0 = pu0, r.pu1 = pu1, r.pv0 = pv0, r.pv1 = pv1;
+    const size_t n = h.size();
+    for (size_t k = 0; k < n && k < 8; ++k) {
+      const auto& a = h[k];
+      const auto& b = h[(k + 1) % n];
+      const double nx = b[1] - a[1], ny = a[0] - b[0];
+      r.edge[k][0] = nx;
+      r.edge[k][1] = ny;
+      r.edge[k][2] = nx * a[0] + ny * a[1];
+    }
+    out->rec.push_back(r);
   }
   return true;
 }

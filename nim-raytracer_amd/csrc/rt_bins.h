@@ -23,6 +23,7 @@
 
 #include "rt_bins_geom.h"
 #include "rt_common.h"
+#include "rt_objgrid_gpu.h"
 
 namespace rtmi {
 
@@ -147,5 +148,16 @@ struct ObjGridHost {
 };
 bool build_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3], ObjGridHost* out,
                              const char** why);
+// The same grid up to its cell loop, for the device builder (rt_objgrid_gpu.h):
+// the header, off_grid, the boxes' growth and one record per bounded object in
+// scene order (none: the 1x1 grid of off_grid). Fails where the builder fails.
+struct ObjGridPlan {
+  LightGrid g;
+  unsigned long long off_grid = 0;
+  double delta = 0.0;
+  std::vector<ObjGridRec> rec;
+};
+bool plan_object_light_grid(const std::vector<ObjBox>& objs, const double dir[3], ObjGridPlan* out,
+                            const char** why);
 
 }  // namespace rtmi

@@ -253,6 +253,154 @@ extern "C" int rtmi_test_relight_passes(rt_scene* s, int32_t enable, float ms[6]
   return RT_OK;
 }
 
+// ---- object updates (rt_scene_set_objects) --------------------------------
+
+// What rt_scene_create forms from the scene's current objects (obj_desc), its
+// meshes' boxes and its lights, on the host, against the device's arrays,
+// byte for byte. out[k]: differing bytes (a length difference counts each
+// missing byte) of 0 f64.objects, 1 f32.objs, 2 f32.objx, 3 objbox_dev, 4 the
+// object-grid headers, 5 the object-grid masks, 6 off_grid, 7 the scalar
+// state (f32_subset's object bits, any_reflective, lean64_plane, skippable,
+// h_obj_ty, obj_meta, the host copy of f32.objs, the mesh object's transform).
+namespace {
+template <class T>
+int64_t diff_host(const DevBuf<T>& a, const std::vector<T>& want, bool present) {
+  const size_t nb = present ? want.size() * sizeof(T) : 0;
+  const size_t na = a.p ? a.bytes() : 0;
+  // (an empty upload still holds one element: DevBuf::alloc)
+  const size_t have = present && want.empty() ? 0 : na;
+  std::vector<unsigned char> ha(have);
+  if (have && hipMemcpy(ha.data(), a.p, have, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const unsigned char* hb = reinterpret_cast<const unsigned char*>(want.data());
+  const size_t n = std::min(have, nb);
+  int64_t bad = (int64_t)(std::max(have, nb) - n);
+  for (size_t k = 0; k < n; ++k) bad += ha[k] != hb[k] ? 1 : 0;
+  return bad;
+}
+}  // namespace
+
+extern "C" int rtmi_test_objects_diff(rt_scene* s, int64_t out[8]) {
+  if (!s || !out) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  HIP_TRY(hipDeviceSynchronize());
+  std::fill(out, out + 8, 0);
+  const rt_object_desc* objs = s->obj_desc.data();
+  const int32_t n = s->nobj;
+  std::vector<DevObject<double>> o64;
+  std::vector<FObj> fo;
+  std::vector<FObjX> fx;
+  fill_objects<double>(objs, n, o64);
+  fill_fast_objects(objs, n, s->h_dm32, fo, fx);
+  out[0] = diff_host(s->f64.objects, o64, true);
+  out[1] = diff_host(s->f32.objs, fo, true);
+  out[2] = diff_host(s->f32.objx, fx, true);
+  std::vector<ObjBox> boxes;
+  std::vector<DevObjBox> ob;
+  const bool bins = n >= 4 && n <= 64;
+  if (bins) {
+    fill_obj_boxes(objs, n, s->h_dm64, boxes);
+    dev_obj_boxes(boxes, ob);
+  }
+  out[3] = diff_host(s->objbox_dev, ob, bins) + (s->objbins != bins);
+  // the object grids by the host builder, as build_lights(device = false) uploads them
+  std::vector<LightGrid> gh((size_t)std::max(1, s->nlight), LightGrid{});
+  std::vector<unsigned long long> gm;
+  unsigned long long off_grid = 0;
+  bool any = false;
+  for (int li = 0; bins && li < s->nlight; ++li) {
+    if (s->light_desc[(size_t)li].type == RT_POINT_LIGHT) continue;
+    ObjGridHost og;
+    const char* why = "";
+    if (!build_object_light_grid(boxes, s->light_desc[(size_t)li].dir, &og, &why)) continue;
+    if ((int64_t)gm.size() + (int64_t)og.masks.size() > INT32_MAX) break;
+    og.g.off_base = (int32_t)gm.size();
+    gm.insert(gm.end(), og.masks.begin(), og.masks.end());
+    gh[(size_t)li] = og.g;
+    off_grid = og.off_grid;
+    any = true;
+  }
+  out[4] = diff_host(s->obj_grids, gh, any) + (s->has_obj_grids != any);
+  out[5] = diff_host(s->obj_grid_mask, gm, any);
+  for (int b = 0; b < 64; ++b) out[6] += ((s->obj_off_grid ^ off_grid) >> b) & 1ull;
+  // the scalar state
+  bool refl = false;
+  const unsigned from_objects = (unsigned)SUB_XF_GENERAL | (unsigned)SUB_REFLECT | (unsigned)SUB_SPHERE |
+                                (unsigned)SUB_BOX | (unsigned)SUB_MESH;
+  const unsigned sub = object_subset(objs, n, &refl);
+  out[7] += (s->f32_subset & from_objects) != sub;
+  out[7] += s->any_reflective != refl;
+  std::vector<rt_scene::ObjMeta> meta;
+  fill_obj_meta(objs, n, meta);
+  out[7] += meta.size() != s->obj_meta.size();
+  for (size_t i = 0; i < meta.size() && i < s->obj_meta.size(); ++i)
+    out[7] += std::memcmp(&meta[i], &s->obj_meta[i], sizeof meta[i]) != 0;
+  out[7] += fo.size() != s->h_fo.size() || s->h_obj_ty.size() != fo.size();
+  for (size_t i = 0; i < fo.size() && i < s->h_fo.size() && i < s->h_obj_ty.size(); ++i)
+    out[7] += (std::memcmp(&fo[i], &s->h_fo[i], sizeof(FObj)) != 0) +
+              (std::memcmp(&fo[i].t[1], &s->h_obj_ty[i], sizeof(float)) != 0);
+  if (s->shadow_mesh >= 0)
+    out[7] += (std::memcmp(s->mesh_o2w, objs[s->shadow_mesh].object_to_world, sizeof s->mesh_o2w) != 0) +
+              (std::memcmp(s->mesh_w2o, objs[s->shadow_mesh].world_to_object, sizeof s->mesh_w2o) != 0);
+  {  // lean64_plane and skippable, as build_lights derives them from obj_meta
+    bool skippable = s->has_grids;
+    for (int i = 0; skippable && i < n; ++i) skippable = i == s->shadow_mesh || objs[i].type == RT_PLANE;
+    int32_t lean = -1;
+    if (skippable && n == 2 && s->nlight >= 1 && s->nlight <= 8) {
+      const int pl = 1 - s->shadow_mesh;
+      bool ok = objs[pl].type == RT_PLANE && !(objs[pl].reflection > 0.0);
+      for (int li = 0; li < s->nlight; ++li) ok = ok && s->light_desc[(size_t)li].type != RT_POINT_LIGHT;
+      if (ok) lean = pl;
+    }
+    out[7] += (s->skippable != skippable) + (s->lean64_plane != lean);
+    if (s->skippable && skippable) {
+      size_t k = 0;
+      for (int i = 0; i < n; ++i) {
+        if (i == s->shadow_mesh) continue;
+        out[7] += k >= s->skip_planes.size() ||
+                  std::memcmp(s->skip_planes[k].o2w, objs[i].object_to_world, sizeof(double) * 16) != 0 ||
+                  std::memcmp(s->skip_planes[k].w2o, objs[i].world_to_object, sizeof(double) * 16) != 0;
+        ++k;
+      }
+    }
+  }
+  for (int k = 0; k < 8; ++k)
+    if (out[k] < 0) return fail(RT_E_DEVICE, "reading the object arrays back failed");
+  return RT_OK;
+}
+
+// The scene's object light grids as they lie on the device: headers (one
+// 64-byte LightGrid per light, up to hdr_cap of them; gu == 0: none) and
+// masks (up to mask_cap), off_grid. Returns the number of masks (0: no object
+// grids), or a negative RT_E_* code.
+extern "C" int64_t rtmi_test_object_grids(rt_scene* s, void* headers, int64_t hdr_cap, unsigned long long* masks,
+                                          int64_t mask_cap, unsigned long long* off_grid) {
+  if (!s || !headers || !masks || !off_grid) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  HIP_TRY(hipDeviceSynchronize());
+  *off_grid = s->obj_off_grid;
+  if (!s->has_obj_grids) return 0;
+  const size_t nh = std::min<size_t>((size_t)std::max<int64_t>(0, hdr_cap), s->obj_grids.n);
+  const size_t nm = std::min<size_t>((size_t)std::max<int64_t>(0, mask_cap), s->obj_grid_mask.n);
+  if (nh) HIP_TRY(hipMemcpy(headers, s->obj_grids.p, nh * sizeof(LightGrid), hipMemcpyDeviceToHost));
+  if (nm) HIP_TRY(hipMemcpy(masks, s->obj_grid_mask.p, nm * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return (int64_t)s->obj_grid_mask.n;
+}
+
+// host != 0: from the next device-path rebuild on (rt_scene_set_objects /
+// _set_lights / _set_mesh_vertices) the object light grids are built by the
+// host builder; 0: by the device builder (the default); < 0: query only. ms
+// (may be null): wall time of the last rebuild's object-grid pass
+// (tools/object_update_bench.py).
+extern "C" int rtmi_test_objgrid_pass(rt_scene* s, int32_t host, double* ms) {
+  if (!s) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (ms) *ms = s->objgrid_ms;
+  if (host >= 0) s->objgrid_host = host != 0;
+  return RT_OK;
+}
+
 // ---- mesh updates (rt_scene_set_mesh_vertices) ----------------------------
 
 namespace {

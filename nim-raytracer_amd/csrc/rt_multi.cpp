@@ -255,6 +255,17 @@ int rt_multi_set_mesh_vertices(rt_multi* m, int32_t mesh, const double* vertices
   return RT_OK;
 }
 
+int rt_multi_set_objects(rt_multi* m, const rt_object_desc* objects, int32_t num_objects) {
+  if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  CurrentDevice keep;
+  for (rt_scene* s : m->scene) {
+    const int rc = rt_scene_set_objects(s, objects, num_objects);
+    if (rc) return rc;
+  }
+  return RT_OK;
+}
+
 int rt_multi_destroy(rt_multi* m) {
   if (!m) return rtmi_fail_msg(RT_E_INVALID, "null argument");
   {

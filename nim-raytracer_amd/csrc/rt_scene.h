@@ -1,6 +1,6 @@
 // rt_scene.h — internal: struct rt_scene (the opaque handle of include/rtmi.h)
 // and what the host units share of it: rtmi.cpp creates and destroys a scene,
-// rt_scene_lights.cpp / rt_scene_mesh.cpp change one, rt_render.cpp and
+// rt_scene_lights.cpp / rt_scene_mesh.cpp / rt_scene_objects.cpp change one, rt_render.cpp and
 // rt_queries.cpp run calls on it, rt_hooks.cpp reads it for the tests. The
 // standard headers below serve those units too.
 #pragma once
@@ -186,6 +186,9 @@ struct rt_scene {
     double reflection, o2w[16], w2o[16];
   };
   std::vector<ObjMeta> obj_meta;
+  // rt_scene_set_objects: the current objects as given (types and meshes as at
+  // create); obj_meta and every object record are formed from them
+  std::vector<rt_object_desc> obj_desc;
   std::vector<int64_t> grid_nent;
   bool mirrors_stale = false;
   double bin_scale = 0.0;          // the grids' length scale of bin_dev (0: not yet reduced)
@@ -255,6 +258,8 @@ struct rt_scene {
   DevBuf<unsigned long long> obj_grid_mask;
   unsigned long long obj_off_grid = 0;
   bool has_obj_grids = false;
+  bool objgrid_host = false;       // relights build the object grids on the host (rtmi_test_objgrid_pass)
+  double objgrid_ms = 0.0;         // the last build's object-grid pass, wall time
   DevBuf<DevObjBox> objbox_dev;
   DevBuf<float> fb_scratch;
   // ray queries (rt_trace_rays* / rt_pick_pixels*): buffers of their own, so a
@@ -340,6 +345,7 @@ struct LightState {
   unsigned long long obj_off_grid = 0;
   bool has_obj_grids = false;
   float ms[6] = {};
+  double objgrid_ms = 0.0;
 };
 
 struct Mapping {
@@ -353,6 +359,24 @@ void dev_obj_boxes(const std::vector<ObjBox>& boxes, std::vector<DevObjBox>& ob)
 // caller is about to replace or free: renders (done, the scene's stream), a
 // pipelined call's build (bstream reads grids and sat_dev), queries.
 int wait_for_calls(rt_scene* s);
+
+// rt_scene_objects.cpp: everything of a scene that is formed from its objects'
+// descriptions alone (and the meshes' boxes and roots). rt_scene_create and
+// rt_scene_set_objects both fill through these, so the two cannot drift apart.
+bool affine(const double* m);
+int32_t classify_xf(const double* w2o, const double* o2w);
+// RT_E_INVALID / RT_E_UNSUPPORTED with the object's index, as rt_scene_create reports them
+int check_objects(const rt_object_desc* objs, int32_t n, int32_t num_meshes);
+template <class R>
+void fill_objects(const rt_object_desc* objs, int32_t n, std::vector<DevObject<R>>& out);
+void fill_fast_objects(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<float>>& dm,
+                       std::vector<FObj>& fo, std::vector<FObjX>& fx);
+// the bin boxes (rt_bins.h ObjBox); dm: the meshes' boxes in float64 (calcAABB)
+void fill_obj_boxes(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<double>>& dm,
+                    std::vector<ObjBox>& boxes);
+void fill_obj_meta(const rt_object_desc* objs, int32_t n, std::vector<rt_scene::ObjMeta>& meta);
+// the SUB_SPHERE / SUB_BOX / SUB_MESH / SUB_XF_GENERAL / SUB_REFLECT bits
+unsigned object_subset(const rt_object_desc* objs, int32_t n, bool* any_reflective);
 
 // rt_scene_lights.cpp
 template <class R>

@@ -1,6 +1,7 @@
 // rt_scene_lights.cpp — everything of a scene that depends on its lights:
 // built by rt_scene_create and rt_scene_set_lights alike (build_lights) and
 // handed to the scene by swapping (adopt_lights).
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -226,13 +227,65 @@ int mesh_grids_device(rt_scene* s, const rt_light_desc* lights, int32_t nl, Ligh
   return RT_OK;
 }
 
+// The object light grids (rt_bins.h) by the device builder
+// (rt_objgrid_gpu.hip): the host plans every distant light's grid (header,
+// cell rectangles, hulls: at most 64 objects each) and one launch writes all
+// the masks; byte for byte what build_lights' host loop uploads.
+int object_grids_device(rt_scene* s, const rt_light_desc* lights, int32_t nl, LightState* L) {
+  std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
+  std::vector<ObjGridLight> gl;
+  std::vector<ObjGridRec> recs;
+  int64_t nmask = 0;
+  int32_t max_cells = 0;
+  for (int li = 0; li < nl; ++li) {
+    if (lights[li].type == RT_POINT_LIGHT) continue;
+    ObjGridPlan pl;
+    const char* why = "";
+    if (!plan_object_light_grid(s->obj_boxes, lights[li].dir, &pl, &why)) continue;
+    const int64_t ncell = (int64_t)pl.g.gu * (int64_t)pl.g.gv;
+    if (nmask + ncell > INT32_MAX) break;  // as the host: this light and every later one go without
+    pl.g.off_base = (int32_t)nmask;
+    gh[(size_t)li] = pl.g;
+    ObjGridLight q;
+    std::memset(&q, 0, sizeof q);
+    q.u0 = (double)pl.g.u0;
+    q.v0 = (double)pl.g.v0;
+    q.hc = 1.0 / (double)pl.g.inv_h;
+    q.delta = pl.delta;
+    q.gu = pl.g.gu;
+    q.gv = pl.g.gv;
+    q.mask_base = (int32_t)nmask;
+    q.rec_base = (int32_t)recs.size();
+    q.nrec = (int32_t)pl.rec.size();
+    gl.push_back(q);
+    recs.insert(recs.end(), pl.rec.begin(), pl.rec.end());
+    nmask += ncell;
+    max_cells = std::max(max_cells, (int32_t)ncell);
+    L->obj_off_grid = pl.off_grid;  // the same set (the unbounded objects) for every light
+  }
+  if (gl.empty()) return RT_OK;
+  int rc;
+  DevBuf<ObjGridLight> d_gl;
+  DevBuf<ObjGridRec> d_rec;
+  if ((rc = L->obj_grids.upload(gh)) || (rc = L->obj_grid_mask.alloc((size_t)nmask)) || (rc = d_gl.upload(gl)) ||
+      (rc = d_rec.upload(recs)))
+    return rc;
+  if (int e = rtmi_object_grids_build(d_gl.p, (int32_t)gl.size(), max_cells, d_rec.p, L->obj_off_grid,
+                                      L->obj_grid_mask.p, s->stream))
+    return fail(e == (int)hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_DEVICE, "object grid build: %s",
+                hipGetErrorString((hipError_t)e));
+  L->has_obj_grids = true;
+  return RT_OK;
+}
+
 }  // namespace
 
 namespace rtmi {
 
 // Builds the scene's light-dependent state for `lights` into *L; reads only
 // what does not depend on the lights (the faces, the objects, the BVH sizes).
-// device: the mesh light grids by the device builder, else by the host's.
+// device: the mesh light grids and the object light grids by the device
+// builders, else by the host's.
 int build_lights(rt_scene* s, const rt_light_desc* lights, int32_t nl, bool device, LightState* L) {
   int rc;
   L->desc.assign(lights, lights + nl);
@@ -280,7 +333,10 @@ int build_lights(rt_scene* s, const rt_light_desc* lights, int32_t nl, bool devi
       }
     }
   }
-  if (s->objbins) {  // the object light grids (rt_bins.h): at most 64 boxes, built on the host
+  const auto t_obj = std::chrono::steady_clock::now();
+  if (s->objbins && device && !s->objgrid_host) {
+    if ((rc = object_grids_device(s, lights, nl, L))) return rc;
+  } else if (s->objbins) {  // the object light grids (rt_bins.h): at most 64 boxes, built on the host
     std::vector<LightGrid> gh((size_t)std::max(1, nl), LightGrid{});
     std::vector<unsigned long long> gm;
     bool any = false;
@@ -301,6 +357,7 @@ int build_lights(rt_scene* s, const rt_light_desc* lights, int32_t nl, bool devi
       L->has_obj_grids = true;
     }
   }
+  L->objgrid_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_obj).count();
   return RT_OK;
 }
 
@@ -338,6 +395,7 @@ void adopt_lights(rt_scene* s, LightState* L) {
   s->obj_off_grid = L->obj_off_grid;
   s->has_obj_grids = L->has_obj_grids;
   std::memcpy(s->relight_ms, L->ms, sizeof s->relight_ms);
+  s->objgrid_ms = L->objgrid_ms;
 }
 
 // The bulky host mirrors of the light grids (cell lists, face boxes, prefix

@@ -151,52 +151,13 @@ int rt_band_rows(int32_t height, int32_t band_h, int32_t world, int32_t* out_row
 
 namespace {
 
-bool affine(const double* m) { return m[3] == 0.0 && m[7] == 0.0 && m[11] == 0.0 && m[15] == 1.0; }
-
-// Identity / pure translation / general (float32 fast paths, DevObject.xf).
-// Translation requires BOTH matrices to have an identity 3x3 block, so the
-// normal transform (object_to_world * n) is the identity too.
-int32_t classify_xf(const double* w2o, const double* o2w) {
-  bool lin_id = true;
-  for (int c = 0; c < 3; ++c)
-    for (int r = 0; r < 3; ++r) {
-      const double id = c == r ? 1.0 : 0.0;
-      if (w2o[c * 4 + r] != id || o2w[c * 4 + r] != id) lin_id = false;
-    }
-  if (!lin_id) return XF_GENERAL;
-  if (w2o[12] == 0.0 && w2o[13] == 0.0 && w2o[14] == 0.0) return XF_IDENTITY;
-  return XF_TRANSLATE;
-}
-
 template <class R>
 void fill_precision(const rt_scene_desc* d, const std::vector<std::vector<double>>& normals,
                     const std::vector<BvhResult>& bvhs, const std::vector<int32_t>& node_base,
                     const std::vector<std::vector<double>>& aabbs, std::vector<DevObject<R>>& objs,
                     std::vector<DevLight<R>>& lights, std::vector<DevMesh<R>>& meshes,
                     std::vector<typename TriOf<R>::type>* tris, std::vector<R>& nrm) {
-  objs.assign((size_t)d->num_objects, DevObject<R>{});
-  for (int i = 0; i < d->num_objects; ++i) {
-    const rt_object_desc& s = d->objects[i];
-    DevObject<R>& o = objs[(size_t)i];
-    for (int k = 0; k < 16; ++k) {
-      o.w2o[k] = (R)s.world_to_object[k];
-      o.o2w[k] = (R)s.object_to_world[k];
-    }
-    o.prm[0] = (R)(s.type == RT_SPHERE ? s.radius : s.box_min[0]);
-    o.prm[1] = (R)s.box_min[1];
-    o.prm[2] = (R)s.box_min[2];
-    o.prm[4] = (R)s.box_max[0];
-    o.prm[5] = (R)s.box_max[1];
-    o.prm[6] = (R)s.box_max[2];
-    for (int k = 0; k < 3; ++k) o.albedo[k] = (R)s.albedo[k];
-    o.albedo[3] = (R)s.reflection;
-    // albedo / PI in R, one correctly rounded IEEE division as the kernel's
-    // (and the oracle's, rt_oracle.c shade) per-sample quotient
-    for (int k = 0; k < 3; ++k) o.albp[k] = (R)s.albedo[k] / (R)3.14159265358979323846;
-    o.type = s.type;
-    o.mesh = s.type == RT_MESH ? s.mesh : 0;
-    o.xf = classify_xf(s.world_to_object, s.object_to_world);
-  }
+  fill_objects<R>(d->objects, d->num_objects, objs);
   fill_lights<R>(d->lights, d->num_lights, lights);
   meshes.assign((size_t)d->num_meshes, DevMesh<R>{});
   int64_t total = 0;
@@ -253,32 +214,7 @@ void fill_precision(const rt_scene_desc* d, const std::vector<std::vector<double
 // float32 kernel records (rt_common.h FObj/FObjX/FMesh/FLight).
 void fill_fast_records(const rt_scene_desc* d, const std::vector<DevMesh<float>>& dm, std::vector<FObj>& fo,
                        std::vector<FObjX>& fx, std::vector<FMesh>& fm, std::vector<FLight>& fl) {
-  const double kPi = 3.14159265358979323846;
-  fo.assign((size_t)d->num_objects, FObj{});
-  fx.assign((size_t)d->num_objects, FObjX{});
-  for (int i = 0; i < d->num_objects; ++i) {
-    const rt_object_desc& s = d->objects[i];
-    FObj& o = fo[(size_t)i];
-    FObjX& x = fx[(size_t)i];
-    o.type = s.type;
-    o.xf = classify_xf(s.world_to_object, s.object_to_world);
-    o.mesh = s.type == RT_MESH ? s.mesh : 0;
-    for (int k = 0; k < 3; ++k) {
-      o.t[k] = (float)s.world_to_object[12 + k];
-      o.lo[k] = (float)(s.type == RT_MESH ? dm[(size_t)s.mesh].lo[k] : s.box_min[k]);
-      o.hi[k] = (float)(s.type == RT_MESH ? dm[(size_t)s.mesh].hi[k] : s.box_max[k]);
-    }
-    // byte offset of the root node in FastData.tree
-    o.root = s.type == RT_MESH && dm[(size_t)s.mesh].root >= 0 ? dm[(size_t)s.mesh].root * (int32_t)sizeof(BvhNode) : -1;
-    o.r = (float)s.radius;
-    for (int c = 0; c < 4; ++c)
-      for (int r = 0; r < 3; ++r) x.w2o[c * 3 + r] = (float)s.world_to_object[c * 4 + r];
-    for (int c = 0; c < 3; ++c)
-      for (int r = 0; r < 3; ++r) x.o2w[c * 3 + r] = (float)s.object_to_world[c * 4 + r];
-    for (int k = 0; k < 3; ++k) x.albedo_pi[k] = (float)(s.albedo[k] / kPi);
-    x.refl = (float)s.reflection;
-    x.normal_base = s.type == RT_MESH ? dm[(size_t)s.mesh].normal_base : 0;
-  }
+  fill_fast_objects(d->objects, d->num_objects, dm, fo, fx);
   fm.assign(dm.size(), FMesh{});
   for (size_t m = 0; m < dm.size(); ++m) {
     for (int k = 0; k < 3; ++k) {
@@ -364,16 +300,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
                  std::chrono::duration<double, std::milli>(now - tp).count());
     tp = now;
   };
-  bool any_reflective = false;
-  for (int i = 0; i < d->num_objects; ++i) {
-    const rt_object_desc& o = d->objects[i];
-    if (o.type < RT_SPHERE || o.type > RT_MESH) return fail(RT_E_INVALID, "object %d: bad type %d", i, o.type);
-    if (o.type == RT_MESH && (o.mesh < 0 || o.mesh >= d->num_meshes))
-      return fail(RT_E_INVALID, "object %d: mesh index %d out of range", i, o.mesh);
-    if (!affine(o.object_to_world) || !affine(o.world_to_object))
-      return fail(RT_E_UNSUPPORTED, "object %d: non-affine transform", i);
-    if (o.reflection > 0.0) any_reflective = true;
-  }
+  if (int orc = check_objects(d->objects, d->num_objects, d->num_meshes)) return orc;
   for (int i = 0; i < d->num_lights; ++i)
     if (d->lights[i].type != RT_DISTANT_LIGHT && d->lights[i].type != RT_POINT_LIGHT)
       return fail(RT_E_INVALID, "light %d: bad type", i);
@@ -482,17 +409,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     if (n_mesh_obj != 1) s->shadow_mesh = -1;
   }
   s->nmesh = d->num_meshes;
-  s->any_reflective = any_reflective;
-  // scene features -> the float32 kernel specialisation (rt_kernels_f32_part.hip)
-  s->f32_subset = 0;
-  for (int i = 0; i < d->num_objects; ++i) {
-    const rt_object_desc& ob = d->objects[i];
-    if (ob.type == RT_SPHERE) s->f32_subset |= SUB_SPHERE;
-    if (ob.type == RT_BOX) s->f32_subset |= SUB_BOX;
-    if (ob.type == RT_MESH) s->f32_subset |= SUB_MESH;
-    if (classify_xf(ob.world_to_object, ob.object_to_world) == XF_GENERAL) s->f32_subset |= SUB_XF_GENERAL;
-  }
-  if (any_reflective) s->f32_subset |= SUB_REFLECT;  // (SUB_POINT: adopt_lights)
+  // scene features -> the float32 kernel specialisation (rt_kernels_f32_part.hip); (SUB_POINT: adopt_lights)
+  s->f32_subset = object_subset(d->objects, d->num_objects, &s->any_reflective);
   s->fov = d->fov;
   std::memcpy(s->c2w, d->camera_to_world, sizeof s->c2w);
   std::memcpy(s->bg, d->bg_color, sizeof s->bg);
@@ -663,17 +581,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     }
   }
   if (d->num_objects >= 4 && d->num_objects <= 64) {  // object bins (rt_bins.h)
-    s->obj_boxes.assign((size_t)d->num_objects, ObjBox{});
-    for (int i = 0; i < d->num_objects; ++i) {
-      const rt_object_desc& ob = d->objects[i];
-      ObjBox& b = s->obj_boxes[(size_t)i];
-      double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-      for (int k = 0; k < 3 && ob.type != RT_PLANE; ++k) {
-        lo[k] = ob.type == RT_SPHERE ? -std::fabs(ob.radius) : ob.type == RT_BOX ? ob.box_min[k] : aabbs[(size_t)ob.mesh][k];
-        hi[k] = ob.type == RT_SPHERE ? std::fabs(ob.radius) : ob.type == RT_BOX ? ob.box_max[k] : aabbs[(size_t)ob.mesh][3 + k];
-      }
-      world_obj_box(ob.type, ob.world_to_object, lo, hi, &b);
-    }
+    fill_obj_boxes(d->objects, d->num_objects, s->h_dm64, s->obj_boxes);
     s->objbins = true;
     std::vector<DevObjBox> ob;
     dev_obj_boxes(s->obj_boxes, ob);
@@ -683,15 +591,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   // everything that depends on the lights (rt_scene_set_lights replaces it)
   s->num_triangles = ntri;
   s->num_nodes = nnodes;
-  s->obj_meta.resize((size_t)d->num_objects);
-  for (int i = 0; i < d->num_objects; ++i) {
-    rt_scene::ObjMeta& om = s->obj_meta[(size_t)i];
-    om.type = d->objects[i].type;
-    om.mesh = d->objects[i].type == RT_MESH ? d->objects[i].mesh : -1;
-    om.reflection = d->objects[i].reflection;
-    std::memcpy(om.o2w, d->objects[i].object_to_world, sizeof om.o2w);
-    std::memcpy(om.w2o, d->objects[i].world_to_object, sizeof om.w2o);
-  }
+  fill_obj_meta(d->objects, d->num_objects, s->obj_meta);
+  s->obj_desc.assign(d->objects, d->objects + d->num_objects);
   {
     LightState ls;
     rc = build_lights(s.get(), d->lights, d->num_lights, false, &ls);

@@ -188,6 +188,7 @@ SIGNATURES = {
     "rt_scene_set_mesh_vertices": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.c_int64,
                                              C.POINTER(C.c_double)]),
     "rt_scene_set_mesh_vertices_device": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P]),
+    "rt_scene_set_objects": (C.c_int, [_P, C.POINTER(rt_object_desc), C.c_int32]),
     "rt_render_lines": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(C.c_float), C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.POINTER(rt_stats)]),
@@ -223,6 +224,7 @@ SIGNATURES = {
     "rt_multi_set_lights": (C.c_int, [_P, C.POINTER(rt_light_desc), C.c_int32]),
     "rt_multi_set_mesh_vertices": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.c_int64,
                                              C.POINTER(C.c_double)]),
+    "rt_multi_set_objects": (C.c_int, [_P, C.POINTER(rt_object_desc), C.c_int32]),
     "rt_multi_destroy": (C.c_int, [_P]),
     "rt_queue_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_queue_start": (C.c_int, [_P]),

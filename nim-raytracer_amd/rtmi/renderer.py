@@ -17,7 +17,7 @@ import numpy as np
 
 from . import abi, glm
 from ._lib import RtmiError, check, lib
-from .scene import Options, Scene, Stats, flatten, flatten_lights
+from .scene import Options, Scene, Stats, flatten, flatten_lights, flatten_objects
 
 
 def initRenderer(device=0):
@@ -44,6 +44,7 @@ class DeviceScene:
         check(lib().rt_scene_create(C.byref(flat.desc), C.byref(h)))
         self.h = h
         self._mesh_ids = [id(g) for g in flat._meshes]  # rt_scene_desc.meshes order (set_mesh_vertices)
+        self._kinds = _object_kinds(flat._objs, len(scene.objects))  # what set_objects keeps
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -77,6 +78,19 @@ class DeviceScene:
         scene then renders exactly as one created with these lights."""
         ls = list(self.scene.lights if lights is None else lights)
         check(lib().rt_scene_set_lights(self.h, flatten_lights(ls), len(ls)))
+
+    def set_objects(self, objects=None):
+        """Scene.objects' placement and materials for the next calls
+        (rt_scene_set_objects): every object's objectToWorld / worldToObject,
+        sphere radius, box bounds, albedo and reflection; None: this
+        DeviceScene's Scene's current objects. The list must hold the same
+        number of objects of the same kinds (and, for meshes, the same
+        TriangleMesh) as at create: TypeError / ValueError otherwise, before
+        the device is touched. Meshes, BVH, lights and camera stay; the scene
+        then answers exactly as one created with these objects."""
+        objs = list(self.scene.objects if objects is None else objects)
+        arr = _checked_objects(objs, self._mesh_ids, self._kinds)
+        check(lib().rt_scene_set_objects(self.h, arr, len(objs)))
 
     def mesh_index(self, mesh):
         """The rt_scene_desc.meshes index of `mesh`: an index, or one of the
@@ -322,27 +336,61 @@ def unshard_bands_device(d_gathered, d_fb, width, height, band_h, world, stream=
                                         int(height), int(band_h), int(world), _stream(stream)))
 
 
+def _object_kinds(arr, n):
+    """(type, mesh) of every object of a flattened list: what an object
+    update must keep."""
+    return [(int(arr[i].type), int(arr[i].mesh)) for i in range(n)]
+
+
+def _checked_objects(objs, mesh_ids, kinds):
+    """The rt_object_desc array of `objs` for an update of a device scene
+    created with `kinds`; ValueError / TypeError when the count, a kind or a
+    mesh differs."""
+    if len(objs) != len(kinds):
+        raise ValueError(f"the device scene has {len(kinds)} objects, not {len(objs)}: set_objects keeps the count")
+    arr, _ = flatten_objects(objs, mesh_ids)
+    for i, (have, want) in enumerate(zip(_object_kinds(arr, len(objs)), kinds)):
+        if have[0] != want[0]:
+            raise TypeError(f"object {i}: its kind differs from the one the device scene was created with")
+        if have[1] != want[1]:
+            raise ValueError(f"object {i}: its mesh differs from the one the device scene was created with")
+    return arr
+
+
 def _shape_key(scene: Scene):
-    """Everything of a Scene except the camera and the lights that the device
-    copy holds: object transforms, materials, sphere radii, the FULL box
-    bounds (all of vmin / vmax, geom.nim:169-170), mesh sizes, background —
-    the fingerprint INTEGRATION.md's Nim binding (shapeHash) keeps; a change
-    rebuilds the device scene. Mesh vertices edited in place (same sizes) are
-    not hashed per call: updateMesh (or invalidateScene, which rebuilds)."""
+    """What the device copy holds of a Scene that no in-place edit replaces:
+    the objects' kinds, sphere radii, the FULL box bounds (all of vmin / vmax,
+    geom.nim:169-170), mesh identity and sizes, background — the fingerprint
+    INTEGRATION.md's Nim binding (shapeHash) keeps; a change rebuilds the
+    device scene. The camera, the lights (_lights_key) and the objects'
+    transforms and materials (_pose_key) are pushed to the copy instead. Mesh
+    vertices edited in place (same sizes) are not hashed per call: updateMesh
+    (or invalidateScene, which rebuilds)."""
     from .scene import Box, Sphere, TriangleMesh
     parts = []
     for o in scene.objects:
         g = o.geometry
-        parts += [type(g).__name__, np.asarray(g.objectToWorld, np.float64).tobytes(),
-                  np.asarray(g.worldToObject, np.float64).tobytes(),
-                  np.asarray(o.material.albedo, np.float64).tobytes(), float(o.material.reflection)]
+        parts.append(type(g).__name__)
         if isinstance(g, Sphere):
             parts.append(g.r)
         elif isinstance(g, Box):
             parts += [g.vmin.tobytes(), g.vmax.tobytes()]
         elif isinstance(g, TriangleMesh):
-            parts += [g.vertices.shape[0], g.faces.shape[0], id(g.vertices), id(g.faces)]
+            parts += [id(g), g.vertices.shape[0], g.faces.shape[0], id(g.vertices), id(g.faces)]
     parts.append(np.asarray(scene.bgColor, np.float64).tobytes())
+    return tuple(parts)
+
+
+def _pose_key(scene: Scene):
+    """Where every object stands and what it is made of (the Nim binding's
+    poseHash): a change is pushed to the existing device copy
+    (rt_scene_set_objects)."""
+    parts = []
+    for o in scene.objects:
+        g = o.geometry
+        parts += [np.asarray(g.objectToWorld, np.float64).tobytes(),
+                  np.asarray(g.worldToObject, np.float64).tobytes(),
+                  np.asarray(o.material.albedo, np.float64).tobytes(), float(o.material.reflection)]
     return tuple(parts)
 
 
@@ -362,10 +410,10 @@ class _Entry:
     the renderLine calls running on it (renders happen outside the cache's
     lock, so a replaced or invalidated copy is closed by whichever comes
     last: the replacement, or the last of those calls)."""
-    __slots__ = ("ds", "shape", "lights", "cam", "fov", "users", "retired")
+    __slots__ = ("ds", "shape", "pose", "lights", "cam", "fov", "users", "retired")
 
-    def __init__(self, ds, shape, lights, cam, fov):
-        self.ds, self.shape, self.lights, self.cam, self.fov = ds, shape, lights, cam, fov
+    def __init__(self, ds, shape, pose, lights, cam, fov):
+        self.ds, self.shape, self.pose, self.lights, self.cam, self.fov = ds, shape, pose, lights, cam, fov
         self.users = 0
         self.retired = False
 
@@ -373,8 +421,9 @@ class _Entry:
 class _DeviceCache:
     """The Nim binding's `deviceScene` in Python: one device
     copy per Scene, created on first use, re-created when the shape key
-    changes, its lights pushed (rt_scene_set_lights) when only Scene.lights
-    changed, its camera pushed (rt_scene_set_camera) when Scene.cameraToWorld
+    changes, its objects' transforms and materials pushed
+    (rt_scene_set_objects) when they moved, its lights pushed
+    (rt_scene_set_lights) when only Scene.lights changed, its camera pushed (rt_scene_set_camera) when Scene.cameraToWorld
     / fov moved — renderLine re-reads them on every call (renderer.nim:135-136,
     150-153). Re-entrant like renderLine (the pool calls it from
     countProcessors() threads at once, workerpool.nim:72-99): lookups,
@@ -402,6 +451,7 @@ class _DeviceCache:
         entry to release() when the call has returned."""
         import weakref
         shape = _shape_key(scene)
+        pose = _pose_key(scene)
         lights = _lights_key(scene)
         cam = np.asarray(scene.cameraToWorld, np.float64).tobytes()
         fov = float(scene.fov)
@@ -410,15 +460,18 @@ class _DeviceCache:
             key = id(scene)
             item = self._entries.get(key)
             e = item[1] if item is not None and item[0]() is scene else None
-            if e is not None and e.shape != shape:  # geometry / materials changed
+            if e is not None and e.shape != shape:  # kinds, sizes or meshes changed
                 stale = self._drop(e)
                 e = None
             if e is None:
                 ds = DeviceScene(scene, device)
                 ds.scene = weakref.proxy(scene)  # the cache must not keep the Scene alive
-                e = _Entry(ds, shape, lights, cam, fov)
+                e = _Entry(ds, shape, pose, lights, cam, fov)
                 self._entries[key] = (weakref.ref(scene, lambda _r, k=key: self._collected(k)), e)
             else:
+                if e.pose != pose:  # objects moved or restyled: the copy takes them, nothing is rebuilt
+                    e.ds.set_objects(scene.objects)
+                    e.pose = pose
                 if e.lights != lights:  # only the lights changed: the copy is relit, not rebuilt
                     e.ds.set_lights(scene.lights)
                     e.lights = lights
@@ -572,6 +625,7 @@ class MultiDeviceScene:
         check(lib().rt_multi_create(C.byref(flat.desc), arr, len(self.devices), int(band_h), C.byref(h)))
         self.h = h
         self._mesh_ids = [id(g) for g in flat._meshes]
+        self._kinds = _object_kinds(flat._objs, len(scene.objects))
 
     def set_camera(self, cameraToWorld, fov):
         """rt_scene_set_camera on every rank's scene."""
@@ -582,6 +636,12 @@ class MultiDeviceScene:
         """rt_scene_set_lights on every rank's scene."""
         ls = list(lights)
         check(lib().rt_multi_set_lights(self.h, flatten_lights(ls), len(ls)))
+
+    def set_objects(self, objects):
+        """rt_scene_set_objects on every rank's scene (DeviceScene.set_objects)."""
+        objs = list(objects)
+        arr = _checked_objects(objs, self._mesh_ids, self._kinds)
+        check(lib().rt_multi_set_objects(self.h, arr, len(objs)))
 
     def set_mesh_vertices(self, mesh, vertices, normals=None):
         """rt_scene_set_mesh_vertices on every rank's scene (host arrays);

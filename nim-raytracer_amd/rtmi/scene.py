@@ -222,39 +222,52 @@ def flatten_lights(lights):
     return out
 
 
+def flatten_objects(objs, mesh_ids=None):
+    """(the rt_object_desc array of a list of Objects, at least one element;
+    the TriangleMesh objects in rt_scene_desc.meshes order): rt_scene_create's
+    and rt_scene_set_objects'. mesh_ids: the id() of every mesh of an existing
+    device scene in that order (an update: the meshes stay, so a TriangleMesh
+    that is not among them is a ValueError); None numbers them as they come."""
+    fixed = mesh_ids is not None
+    mesh_index = {k: i for i, k in enumerate(mesh_ids or ())}
+    meshes = []
+    out = (abi.rt_object_desc * max(1, len(objs)))()
+    for i, ob in enumerate(objs):
+        g = ob.geometry
+        d = out[i]
+        d.object_to_world = _d(flat(g.objectToWorld), 16)
+        d.world_to_object = _d(flat(g.worldToObject), 16)
+        d.albedo = _d(ob.material.albedo, 3)
+        d.reflection = float(ob.material.reflection)
+        d.mesh = -1
+        if isinstance(g, Sphere):
+            d.type = abi.RT_SPHERE
+            d.radius = g.r
+        elif isinstance(g, Plane):
+            d.type = abi.RT_PLANE
+        elif isinstance(g, Box):
+            d.type = abi.RT_BOX
+            d.box_min = _d(g.vmin, 3)
+            d.box_max = _d(g.vmax, 3)
+        elif isinstance(g, TriangleMesh):
+            d.type = abi.RT_MESH
+            if id(g) not in mesh_index:
+                if fixed:
+                    raise ValueError(f"object {i}: its mesh is not one of the scene's TriangleMesh objects")
+                mesh_index[id(g)] = len(meshes)
+                meshes.append(g)
+            d.mesh = mesh_index[id(g)]
+        else:
+            raise TypeError(f"unsupported geometry {type(g).__name__}")
+    return out, meshes
+
+
 class FlatScene:
     """rt_scene_desc plus the buffers it points into (kept alive together)."""
 
     def __init__(self, scene: Scene):
         objs = scene.objects
-        self._meshes = []
-        mesh_index = {}
-        self._objs = (abi.rt_object_desc * max(1, len(objs)))()
-        for i, ob in enumerate(objs):
-            g = ob.geometry
-            d = self._objs[i]
-            d.object_to_world = _d(flat(g.objectToWorld), 16)
-            d.world_to_object = _d(flat(g.worldToObject), 16)
-            d.albedo = _d(ob.material.albedo, 3)
-            d.reflection = float(ob.material.reflection)
-            d.mesh = -1
-            if isinstance(g, Sphere):
-                d.type = abi.RT_SPHERE
-                d.radius = g.r
-            elif isinstance(g, Plane):
-                d.type = abi.RT_PLANE
-            elif isinstance(g, Box):
-                d.type = abi.RT_BOX
-                d.box_min = _d(g.vmin, 3)
-                d.box_max = _d(g.vmax, 3)
-            elif isinstance(g, TriangleMesh):
-                d.type = abi.RT_MESH
-                if id(g) not in mesh_index:
-                    mesh_index[id(g)] = len(self._meshes)
-                    self._meshes.append(g)
-                d.mesh = mesh_index[id(g)]
-            else:
-                raise TypeError(f"unsupported geometry {type(g).__name__}")
+        self._objs, self._meshes = flatten_objects(objs)
         self._mdesc = (abi.rt_mesh_desc * max(1, len(self._meshes)))()
         for i, g in enumerate(self._meshes):
             m = self._mdesc[i]
