@@ -117,7 +117,12 @@ typedef struct rt_light_desc {
 typedef enum rt_bvh_builder {
   RT_BVH_SAH = 0,  /* host binned SAH (32 bins, leaves <= 4 faces): best tracing */
   RT_BVH_PLOC = 1  /* on the device: Morton sort + PLOC clustering + SAH leaf
-                      collapse, same node format; ~100x faster to build      */
+                      collapse, same node format; ~100x faster to build. A
+                      mesh whose clustered tree is deeper than the kernels'
+                      traversal stack (60; boxes nested around one corner,
+                      such as a fan of geometrically growing faces) is built
+                      by the host builder instead: a mesh RT_BVH_SAH accepts
+                      is never refused here                                  */
 } rt_bvh_builder;
 
 /* Scene (src/renderer/scene.nim:11-18). */
@@ -296,7 +301,9 @@ int rt_device_count(void);
 /* ---- scene ------------------------------------------------------------- */
 
 /* Flatten, build the per-mesh BVH and upload everything to the current
- * device. desc and all arrays it points to may be freed after return. */
+ * device. desc and all arrays it points to may be freed after return.
+ * RT_E_INVALID, under either builder, for a non-finite vertex that a face
+ * references (as rt_scene_set_mesh_vertices). */
 int rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene);
 /* Waits for a call still running on the scene in another thread, then frees
  * it. No call may START on a scene once its destroy has begun (the caller's

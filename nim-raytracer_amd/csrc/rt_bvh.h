@@ -35,7 +35,9 @@ bool build_bvh(const double* vertices, const int32_t* faces, int64_t nf, const B
 
 // Device builder (rt_bvh_gpu.hip): PLOC clustering + SAH collapse on the
 // current HIP device, same node format, leaf limit and conservative bounds.
-// d_vertices / d_faces are device copies of the mesh arrays.
+// d_vertices / d_faces are device copies of the mesh arrays. The clustering
+// has no depth bound: a tree deeper than kMaxBvhDepth is declined with
+// out->max_depth set to its depth (rt_scene_create then takes build_bvh).
 bool build_bvh_device(const double* d_vertices, const int32_t* d_faces, int64_t nf, const BvhBuildParams& prm,
                       BvhResult* out, const char** err);
 

@@ -499,6 +499,50 @@ uint64_t fnv(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
   return h;
 }
 
+// One mesh's nodes of the scene's host copy (h_nodes) as its builder returned
+// them: child and face references relative to the mesh.
+BvhResult mesh_tree(const rt_scene* s, const rt_scene::MeshKeep& keep, const std::vector<int32_t>& order) {
+  BvhResult r;
+  r.order = order;
+  r.nodes.assign(s->h_nodes.begin() + keep.node_base, s->h_nodes.begin() + keep.node_base + keep.node_count);
+  for (BvhNode& nd : r.nodes) {
+    if (nd.n0 == 0 && nd.c0 >= 0) nd.c0 -= keep.node_base;
+    if (nd.n1 == 0 && nd.c1 >= 0) nd.c1 -= keep.node_base;
+    if (nd.n0 > 0) nd.c0 -= (int32_t)keep.tri_base;
+    if (nd.n1 > 0) nd.c1 -= (int32_t)keep.tri_base;
+  }
+  return r;
+}
+
+// refit_bvh of the topology `topo` (mesh_tree) on the vertices v against the
+// boxes of three copies of the mesh's nodes: topo itself (host_boxes), the
+// float64 kernels' node array (boxes64) and the float32 tree (boxes32), 48
+// box bytes per node; children: the child references and counts of the two
+// device copies against h_nodes. The counters are added to.
+int refit_diff(const rt_scene* s, const rt_scene::MeshKeep& keep, const BvhResult& topo, const std::vector<double>& v,
+               const std::vector<int32_t>& f, const std::vector<BvhNode>& nodes, const std::vector<BvhNode>& tree,
+               int64_t* host_boxes, int64_t* boxes64, int64_t* boxes32, int64_t* children) {
+  BvhResult r = topo;
+  const char* err = "";
+  if (!refit_bvh(v.data(), f.data(), keep.nf, &r, &err)) return fail(RT_E_INVALID, "%s", err);
+  const int64_t nnodes = s->num_nodes;
+  const int32_t kB = (int32_t)sizeof(BvhNode);
+  for (int32_t k = 0; k < keep.node_count; ++k) {
+    const BvhNode& want = r.nodes[(size_t)k];
+    const BvhNode& topo_n = s->h_nodes[(size_t)(keep.node_base + k)];
+    const BvhNode& a = nodes[(size_t)(keep.node_base + k)];
+    const BvhNode& b = tree[(size_t)(keep.node_base + k)];
+    *host_boxes += std::memcmp(topo_n.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+    *boxes64 += std::memcmp(a.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+    *boxes32 += std::memcmp(b.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+    *children += (a.c0 != topo_n.c0) + (a.c1 != topo_n.c1) + (a.n0 != topo_n.n0) + (a.n1 != topo_n.n1);
+    *children += (b.c0 != (topo_n.n0 > 0 ? (int32_t)nnodes + topo_n.c0 : topo_n.c0) * kB) +
+                 (b.c1 != (topo_n.n1 > 0 ? (int32_t)nnodes + topo_n.c1 : topo_n.c1) * kB) + (b.n0 != topo_n.n0) +
+                 (b.n1 != topo_n.n1);
+  }
+  return RT_OK;
+}
+
 }  // namespace
 
 // The host create path on the scene's current vertices (records, normals,
@@ -638,30 +682,10 @@ extern "C" int rtmi_test_mesh_update_diff(rt_scene* s, int64_t out[16]) {
     }
     // the host refit of this mesh's nodes as created
     if (keep.node_count > 0) {
-      BvhResult r;
-      r.order = order;
-      r.nodes.assign(s->h_nodes.begin() + keep.node_base, s->h_nodes.begin() + keep.node_base + keep.node_count);
-      for (BvhNode& nd : r.nodes) {
-        if (nd.n0 == 0 && nd.c0 >= 0) nd.c0 -= keep.node_base;
-        if (nd.n1 == 0 && nd.c1 >= 0) nd.c1 -= keep.node_base;
-        if (nd.n0 > 0) nd.c0 -= (int32_t)keep.tri_base;
-        if (nd.n1 > 0) nd.c1 -= (int32_t)keep.tri_base;
-      }
-      const char* err = "";
-      if (!refit_bvh(v.data(), f.data(), keep.nf, &r, &err)) return fail(RT_E_INVALID, "mesh %d: %s", m, err);
-      const int32_t kB = (int32_t)sizeof(BvhNode);
-      for (int32_t k = 0; k < keep.node_count; ++k) {
-        const BvhNode& want = r.nodes[(size_t)k];
-        const BvhNode& topo = s->h_nodes[(size_t)(keep.node_base + k)];
-        const BvhNode& a = nodes[(size_t)(keep.node_base + k)];
-        const BvhNode& b = tree[(size_t)(keep.node_base + k)];
-        out[5] += std::memcmp(a.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
-        out[6] += std::memcmp(b.lo0, want.lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
-        out[7] += (a.c0 != topo.c0) + (a.c1 != topo.c1) + (a.n0 != topo.n0) + (a.n1 != topo.n1);
-        out[7] += (b.c0 != (topo.n0 > 0 ? (int32_t)nnodes + topo.c0 : topo.c0) * kB) +
-                  (b.c1 != (topo.n1 > 0 ? (int32_t)nnodes + topo.c1 : topo.c1) * kB) + (b.n0 != topo.n0) +
-                  (b.n1 != topo.n1);
-      }
+      const BvhResult r = mesh_tree(s, keep, order);
+      int64_t host_boxes = 0;
+      if (int rc = refit_diff(s, keep, r, v, f, nodes, tree, &host_boxes, &out[5], &out[6], &out[7]))
+        return fail(rc, "mesh %d: %s", m, rt_last_error());
     }
   }
   std::vector<DevMesh<double>> d_dm64;
@@ -723,5 +747,191 @@ extern "C" int rtmi_test_mesh_update_passes(rt_scene* s, int32_t enable, float m
   std::lock_guard<std::mutex> lk(s->mu);
   if (ms) std::copy(s->mesh_ms, s->mesh_ms + 6, ms);
   s->mesh_timed = enable != 0;
+  return RT_OK;
+}
+
+// ---- tree checker (tests/test_bvh_corpus_cpu.py, tests/test_gpu_bvh.py) ----
+
+namespace {
+
+enum {  // out[] of the two checker hooks; 0 - 7 are counters a sound tree leaves at zero
+  kChkInvalid = 0,    // validate_bvh fails, or the walk from the root does not reach every node once
+  kChkUncontained,    // faces outside one of their ancestors' boxes (uncontained, the builders' margin)
+  kChkBigLeaves,      // leaves of more than kLeafMax faces
+  kChkLayout,         // inner children that are not at their depth-first index
+  kChkHostBoxes,      // nodes whose 48 box bytes differ from refit_bvh of the same topology
+  kChkBoxes64,        // the same for the float64 kernels' node array (device hook only)
+  kChkBoxes32,        // the same for the float32 tree (device hook only)
+  kChkChildren,       // child references and counts of the two device copies (device hook only)
+  kChkLeafMax,        // the largest leaf
+  kChkDepth,          // depth walked from the root (root = 1, inner nodes)
+  kChkReported,       // the depth the builder / the scene reports
+  kChkNodes,          // nodes
+  kChkWords
+};
+
+double half_area(const float* lo, const float* hi) {
+  const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
+  return dx * dy + dy * dz + dz * dx;
+}
+
+// What is checked of the tree itself (no refit): counters 0 - 3, words 8, 9,
+// 11, and the SAH cost with cost_node = cost_tri = 1: the sum over inner nodes
+// of half-area(node) / half-area(root) plus the sum over leaves of
+// n * half-area(leaf) / half-area(root); 0 when the root's area is 0. A node's
+// box is the union of its two child boxes.
+void check_tree(const BvhResult& r, const double* v, const int32_t* f, int64_t nf, int64_t* out, double* cost) {
+  const char* err = "";
+  *cost = 0.0;
+  out[kChkNodes] = (int64_t)r.nodes.size();
+  if (!validate_bvh(r, nf, &err)) {
+    out[kChkInvalid] = 1;
+    return;
+  }
+  const size_t nn = r.nodes.size();
+  if (nn == 0) return;
+  const bool single = nn == 1 && r.nodes[0].n0 > 0 && r.nodes[0].c0 == r.nodes[0].c1;
+  // parents before children, every node once
+  std::vector<int32_t> pre, depth(nn, 0), inner(nn, 0);
+  std::vector<unsigned char> seen(nn, 0);
+  pre.push_back(0);
+  depth[0] = 1;
+  seen[0] = 1;
+  for (size_t k = 0; k < pre.size(); ++k) {
+    const BvhNode& nd = r.nodes[(size_t)pre[k]];
+    for (int slot = 0; slot < 2; ++slot) {
+      const int32_t c = slot ? nd.c1 : nd.c0, n = slot ? nd.n1 : nd.n0;
+      if (n > 0) continue;
+      if (seen[(size_t)c]) {
+        out[kChkInvalid] = 1;
+        return;
+      }
+      seen[(size_t)c] = 1;
+      depth[(size_t)c] = depth[(size_t)pre[k]] + 1;
+      pre.push_back(c);
+    }
+  }
+  if (pre.size() != nn) {
+    out[kChkInvalid] = 1;
+    return;
+  }
+  auto node_area = [&](const BvhNode& nd) {
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(nd.lo0[a], nd.lo1[a]);
+      hi[a] = std::max(nd.hi0[a], nd.hi1[a]);
+    }
+    return half_area(lo, hi);
+  };
+  const double root_area = node_area(r.nodes[0]);
+  double sum = 0.0;
+  for (size_t k = nn; k-- > 0;) {
+    const int32_t i = pre[k];
+    const BvhNode& nd = r.nodes[(size_t)i];
+    inner[(size_t)i] = 1 + (nd.n0 == 0 ? inner[(size_t)nd.c0] : 0) + (nd.n1 == 0 ? inner[(size_t)nd.c1] : 0);
+    out[kChkDepth] = std::max<int64_t>(out[kChkDepth], depth[(size_t)i]);
+    if (nd.n0 == 0 && nd.c0 != i + 1) ++out[kChkLayout];
+    if (nd.n1 == 0 && nd.c1 != i + 1 + (nd.n0 == 0 ? inner[(size_t)nd.c0] : 0)) ++out[kChkLayout];
+    sum += node_area(nd);
+    for (int slot = 0; slot < (single ? 1 : 2); ++slot) {
+      const int32_t n = slot ? nd.n1 : nd.n0;
+      if (n == 0) continue;
+      out[kChkLeafMax] = std::max<int64_t>(out[kChkLeafMax], n);
+      if (n > kLeafMax) ++out[kChkBigLeaves];
+      sum += (double)n * (slot ? half_area(nd.lo1, nd.hi1) : half_area(nd.lo0, nd.hi0));
+    }
+  }
+  *cost = root_area > 0.0 ? sum / root_area : 0.0;
+  double inflate = 0.0;
+  std::vector<AncBox> anc;
+  if (!bvh_margin(v, f, nf, &inflate)) {
+    out[kChkInvalid] = 1;
+    return;
+  }
+  out[kChkUncontained] = uncontained(r, v, f, inflate, 0, anc);
+}
+
+}  // namespace
+
+// CPU only: the host SAH builder (build_bvh) on these arrays, its tree through
+// the checker. out: 12 words (kChk* above; the device copies' counters stay
+// zero), cost: 1. RT_E_INVALID, with the builder's message, when it declines.
+// defect (0: none) spoils the tree before it is checked, to show what the
+// checker sees: 1 the last node's first box ends below where it starts, 2 the
+// root's two children change places, 4 the reported depth is one too many.
+extern "C" int rtmi_test_bvh_check_host(const double* v, int64_t nv, const int32_t* faces, int64_t nf, int32_t defect,
+                                        int64_t out[12], double cost[1]) {
+  if (!v || !faces || !out || !cost || nv <= 0 || nf <= 0) return fail(RT_E_INVALID, "bad argument");
+  for (int64_t k = 0; k < 3 * nf; ++k)
+    if (faces[k] < 0 || faces[k] >= nv) return fail(RT_E_INVALID, "face index out of range");
+  std::fill(out, out + kChkWords, 0);
+  BvhResult r;
+  const char* err = "";
+  BvhBuildParams prm;
+  if (!build_bvh(v, faces, nf, prm, &r, &err)) return fail(RT_E_INVALID, "%s", err);
+  out[kChkReported] = r.max_depth + (defect == 4 ? 1 : 0);
+  if (defect == 1) r.nodes.back().hi0[0] = r.nodes.back().lo0[0] - 1.0f;
+  if (defect == 2) {
+    BvhNode& n0 = r.nodes[0];
+    std::swap(n0.c0, n0.c1);
+    std::swap(n0.n0, n0.n1);
+    for (int a = 0; a < 3; ++a) {
+      std::swap(n0.lo0[a], n0.lo1[a]);
+      std::swap(n0.hi0[a], n0.hi1[a]);
+    }
+  }
+  check_tree(r, v, faces, nf, out, cost);
+  BvhResult fit = r;
+  if (!refit_bvh(v, faces, nf, &fit, &err)) return fail(RT_E_INVALID, "%s", err);
+  for (size_t k = 0; k < r.nodes.size(); ++k)
+    out[kChkHostBoxes] += std::memcmp(r.nodes[k].lo0, fit.nodes[k].lo0, 12 * sizeof(float)) != 0 ? 1 : 0;
+  return RT_OK;
+}
+
+// One mesh of a live scene: its kept vertices, faces and leaf order, its nodes
+// in h_nodes (rebased as rtmi_test_mesh_update_diff rebases them), in the
+// float64 kernels' node array and in the float32 tree, through the checker.
+// out: 12 words (kChk* above), cost: 1.
+extern "C" int rtmi_test_bvh_check(rt_scene* s, int32_t mesh, int64_t out[12], double cost[1]) {
+  if (!s || !out || !cost || mesh < 0 || mesh >= s->nmesh) return fail(RT_E_INVALID, "bad argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  HIP_TRY(hipDeviceSynchronize());
+  std::fill(out, out + kChkWords, 0);
+  const rt_scene::MeshKeep& keep = s->mesh_keep[(size_t)mesh];
+  std::vector<double> v;
+  std::vector<int32_t> f, order;
+  std::vector<BvhNode> tree, nodes;
+  if (!download(keep.verts.p, (size_t)keep.nv * 3, v) || !download(keep.faces.p, (size_t)keep.nf * 3, f) ||
+      !download(keep.order.p, (size_t)keep.nf, order) || !download(s->f32.tree.p, (size_t)s->num_nodes, tree) ||
+      !download(s->nodes.p, (size_t)s->num_nodes, nodes))
+    return fail(RT_E_DEVICE, "reading the mesh arrays back failed");
+  const BvhResult r = mesh_tree(s, keep, order);
+  out[kChkReported] = s->max_depth;
+  check_tree(r, v.data(), f.data(), keep.nf, out, cost);
+  if (out[kChkInvalid]) return RT_OK;
+  return refit_diff(s, keep, r, v, f, nodes, tree, &out[kChkHostBoxes], &out[kChkBoxes64], &out[kChkBoxes32],
+                    &out[kChkChildren]);
+}
+
+// The device builder alone (build_bvh_device, no scene) on these arrays, on
+// the current device. out[0]: it accepts the mesh (1 / 0: rt_last_error has
+// its reason), out[1]: the depth of the tree it formed, which it reports even
+// when it declines the tree for that depth, out[2]: nodes.
+extern "C" int rtmi_test_ploc_raw(const double* v, int64_t nv, const int32_t* faces, int64_t nf, int64_t out[3]) {
+  if (!v || !faces || !out || nv <= 0 || nf <= 0) return fail(RT_E_INVALID, "bad argument");
+  for (int64_t k = 0; k < 3 * nf; ++k)
+    if (faces[k] < 0 || faces[k] >= nv) return fail(RT_E_INVALID, "face index out of range");
+  DevBuf<double> dv;
+  DevBuf<int32_t> df;
+  if (int rc = dv.upload(v, (size_t)nv * 3)) return rc;
+  if (int rc = df.upload(faces, (size_t)nf * 3)) return rc;
+  BvhResult r;
+  const char* err = "";
+  BvhBuildParams prm;
+  out[0] = build_bvh_device(dv.p, df.p, nf, prm, &r, &err) ? 1 : 0;
+  out[1] = r.max_depth;
+  out[2] = (int64_t)r.nodes.size();
+  if (!out[0]) (void)fail(RT_E_DEVICE, "%s", err);
   return RT_OK;
 }

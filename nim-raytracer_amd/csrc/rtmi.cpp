@@ -5,6 +5,7 @@
 // is flattened and uploaded once (rt_scene_create), then whole frames, row
 // ranges (the pool's scanline messages, src/raytracer.nim:25-32) or
 // multi-GPU bands are rendered by the gfx950 kernels in rt_device.h.
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -371,11 +372,31 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     mark("mesh upload");
     const char* err = "BVH build failed";
     BvhBuildParams prm;
-    const bool ok = d->bvh_builder == RT_BVH_PLOC
-                        ? build_bvh_device(d_verts[(size_t)m].p, d_faces[(size_t)m].p, md.num_faces, prm,
-                                           &bvhs[(size_t)m], &err)
-                        : build_bvh(md.vertices, md.faces, md.num_faces, prm, &bvhs[(size_t)m], &err);
-    if (!ok) return fail(d->bvh_builder == RT_BVH_PLOC ? RT_E_DEVICE : RT_E_INVALID, "mesh %d: %s", m, err);
+    // a face's vertices are finite under either builder (their min / max
+    // pass over a NaN, so neither sees one; rt_scene_set_mesh_vertices declines it too)
+    std::atomic<bool> finite{true};
+    parallel_for(md.num_faces, [&](int64_t fb, int64_t fe) {
+      bool all = true;
+      for (int64_t k = 3 * fb; k < 3 * fe; ++k) {
+        const double* p = &md.vertices[3 * (size_t)md.faces[k]];
+        all = all && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+      }
+      if (!all) finite = false;
+    });
+    if (!finite) return fail(RT_E_INVALID, "mesh %d: mesh has non-finite vertices", m);
+    bool device_built = d->bvh_builder == RT_BVH_PLOC;
+    bool ok = device_built ? build_bvh_device(d_verts[(size_t)m].p, d_faces[(size_t)m].p, md.num_faces, prm,
+                                              &bvhs[(size_t)m], &err)
+                           : build_bvh(md.vertices, md.faces, md.num_faces, prm, &bvhs[(size_t)m], &err);
+    // The clustering has no depth bound: boxes nested around a shared corner
+    // (a fan of geometrically growing faces) merge one pair a round into a
+    // chain as deep as their count. The host builder splits at the object
+    // median past depth 38, so a mesh it accepts is never refused here.
+    if (!ok && device_built && bvhs[(size_t)m].max_depth > kMaxBvhDepth) {
+      device_built = false;
+      ok = build_bvh(md.vertices, md.faces, md.num_faces, prm, &bvhs[(size_t)m], &err);
+    }
+    if (!ok) return fail(device_built ? RT_E_DEVICE : RT_E_INVALID, "mesh %d: %s", m, err);
     mark("bvh build");
     node_base[(size_t)m] = (int32_t)all_nodes.size();
     for (BvhNode nd : bvhs[(size_t)m].nodes) {

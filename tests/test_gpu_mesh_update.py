@@ -27,6 +27,8 @@ from rtmi.renderer import (DeviceScene, MultiDeviceScene, band_rows, deviceScene
 from rtmi.renderer import _cache
 from rtmi.scene import DistantLight, TriangleMesh
 
+from bvh_corpus import coincident as _coincident, flat_grid as _flat_grid, soup as _soup
+
 pytestmark = pytest.mark.gpu
 
 BIAS = 1e-4
@@ -35,34 +37,7 @@ DIFF_NAMES = ["trifast", "trif64", "n32", "n64", "bins", "boxes64", "boxes32", "
 RELIGHT_NAMES = ["headers", "off", "ent", "sat", "lrec", "grec", "flight", "dlight"]
 
 
-# ---- meshes (as tests/test_gpu_bvh.py builds them) -----------------------------
-
-def _soup(n, seed):
-    rng = np.random.default_rng(seed)
-    c = rng.uniform(-2.0, 2.0, (n, 1, 3)) + np.array([0.0, 2.0, 0.0])
-    v = (c + rng.normal(0.0, 0.6, (n, 3, 3))).reshape(-1, 3)
-    return TriangleMesh(v, np.arange(3 * n, dtype=np.int32).reshape(-1, 3))
-
-
-def _coincident():
-    base = np.array([[-1.0, 1.0, 0.0], [1.0, 1.0, 0.0], [0.0, 3.0, 0.0]])
-    v = np.concatenate([np.tile(base, (64, 1)), base + [2.5, 0.0, 0.5], base + [-2.5, 0.0, -0.5],
-                        base + [0.0, 0.5, 1.0]])
-    return TriangleMesh(v, np.arange(len(v), dtype=np.int32).reshape(-1, 3))
-
-
-def _flat_grid(k=32):
-    xs = np.linspace(-3.0, 3.0, k + 1)
-    zs = np.linspace(-2.0, 2.0, k + 1)
-    X, Z = np.meshgrid(xs, zs, indexing="ij")
-    v = np.stack([X.ravel(), np.full(X.size, 1.5), Z.ravel()], 1)
-    f = []
-    for i in range(k):
-        for j in range(k):
-            a, b, c, d = i * (k + 1) + j, (i + 1) * (k + 1) + j, (i + 1) * (k + 1) + j + 1, i * (k + 1) + j + 1
-            f += [[a, d, b], [b, d, c]]
-    return TriangleMesh(v, np.array(f, np.int32))
-
+# ---- meshes (tests/bvh_corpus.py) -----------------------------------------------
 
 def _scene(mesh):
     return scenes._mesh_scene(mesh, "m", (0.7, 0.6, 0.5))

@@ -18,9 +18,11 @@ from rtmi.abi import RT_BVH_PLOC, RT_BVH_SAH
 from rtmi.renderer import DeviceScene
 from rtmi.scene import Box, Material, Object, Plane, Scene, Sphere, TriangleMesh, initBox, initPlane, initSphere
 
+from bvh_corpus import coincident as _coincident, flat_grid as _flat_grid
+from query_checks import INF, Got, Ref, _dev, check, check_stats, same_bits, trace
+
 pytestmark = pytest.mark.gpu
 
-INF = float("inf")
 N_RAYS = 2000
 SCALES = (0.01, 1.0, 100.0)
 
@@ -83,24 +85,6 @@ def make_rays(name, n=N_RAYS):
     return np.ascontiguousarray(orig), np.ascontiguousarray(d)
 
 
-class Ref:
-    """The oracle's answers for one batch."""
-
-    def __init__(self, osc, orig, dirs, tnear=None):
-        n = len(orig)
-        self.obj = np.empty(n, np.int32)
-        self.face = np.empty(n, np.int32)
-        self.t = np.empty(n, np.float64)
-        self.tests = np.zeros(n, np.int64)
-        self.hits = np.zeros(n, np.int64)
-        o4 = np.concatenate([orig, np.ones((n, 1))], 1)
-        d4 = np.concatenate([dirs, np.zeros((n, 1))], 1)
-        for i in range(n):
-            ob, t, tri, st = osc.trace(o4[i], d4[i], INF if tnear is None else float(tnear[i]))
-            self.obj[i], self.t[i], self.face[i] = ob, t, tri if ob >= 0 else -1
-            self.tests[i], self.hits[i] = st.numIntersectionTests, st.numIntersectionHits
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle_scene(name):
     import oracle
@@ -121,47 +105,6 @@ def ref(name, scale):
 @functools.lru_cache(maxsize=None)
 def device_scene(name, builder=RT_BVH_SAH):
     return DeviceScene(SCENES[name](), bvh_builder=builder)
-
-
-# ---- the device side -----------------------------------------------------------
-def _dev(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-
-class Got:
-    def __init__(self, res, normals=False):
-        res = list(res)
-        self.t, self.obj, self.face = (np.ascontiguousarray(x.cpu().numpy()) for x in res[:3])
-        self.normals = res[3].cpu().numpy() if normals else None
-        self.stats = res[-1]
-
-    def raw(self):
-        n = b"" if self.normals is None else self.normals.tobytes()
-        return self.t.tobytes() + self.obj.tobytes() + self.face.tobytes() + n
-
-
-def trace(ds, orig, dirs, tnear=None, normals=False, **kw):
-    return Got(ds.trace_rays(_dev(orig), _dev(dirs), _dev(tnear), normals=normals, stats=True, **kw), normals)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
-
-
-def check(got, want, sel=None):
-    """got == the oracle's answers (for the rays in sel), Stats included."""
-    sel = slice(None) if sel is None else sel
-    assert np.array_equal(got.obj[sel], want.obj[sel])
-    assert np.array_equal(got.face[sel], want.face[sel])
-    assert same_bits(got.t[sel], want.t[sel])
-
-
-def check_stats(got, want, sel=None):
-    sel = slice(None) if sel is None else sel
-    assert got.stats.numIntersectionTests == int(want.tests[sel].sum())
-    assert got.stats.numIntersectionHits == int(want.hits[sel].sum())
-    assert got.stats.numPrimaryRays == got.stats.numShadowRays == got.stats.numReflectionRays == 0
 
 
 # ---- 1. oracle parity ----------------------------------------------------------
@@ -256,28 +199,6 @@ def test_degenerate_rays_are_masked(gpu, oracle_mod):
 
 
 # ---- 3. edges of the rule ------------------------------------------------------
-def _coincident():
-    """64 copies of one face (exact t ties) plus 3 others (tests/test_gpu_bvh.py)."""
-    base = np.array([[-1.0, 1.0, 0.0], [1.0, 1.0, 0.0], [0.0, 3.0, 0.0]])
-    v = np.concatenate([np.tile(base, (64, 1)), base + [2.5, 0.0, 0.5], base + [-2.5, 0.0, -0.5],
-                        base + [0.0, 0.5, 1.0]])
-    return TriangleMesh(v, np.arange(len(v), dtype=np.int32).reshape(-1, 3))
-
-
-def _flat_grid(k=32):
-    """A k x k quad grid in the plane y = 1.5 (tests/test_gpu_bvh.py)."""
-    xs = np.linspace(-3.0, 3.0, k + 1)
-    zs = np.linspace(-2.0, 2.0, k + 1)
-    X, Z = np.meshgrid(xs, zs, indexing="ij")
-    v = np.stack([X.ravel(), np.full(X.size, 1.5), Z.ravel()], 1)
-    f = []
-    for i in range(k):
-        for j in range(k):
-            a, b, c, d = i * (k + 1) + j, (i + 1) * (k + 1) + j, (i + 1) * (k + 1) + j + 1, i * (k + 1) + j + 1
-            f += [[a, d, b], [b, d, c]]
-    return TriangleMesh(v, np.array(f, np.int32))
-
-
 def _axis_rays(points):
     """Every axis direction with every sign of its two zero components, from every point."""
     dirs = []
