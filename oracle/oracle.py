@@ -61,6 +61,8 @@ def _load():
     lib.oracle_trace.restype = C.c_int32
     lib.oracle_trace.argtypes = [P, dp, dp, C.c_double, dp, C.POINTER(C.c_int64),
                                  C.POINTER(abi.rt_stats)]
+    lib.oracle_hit_normal.restype = None
+    lib.oracle_hit_normal.argtypes = [P, dp, dp, C.c_int32, C.c_double, C.c_int64, dp]
     lib.oracle_calc_pixel.restype = None
     lib.oracle_calc_pixel.argtypes = [P, C.POINTER(abi.rt_options), C.c_int32, C.c_int32, dp,
                                       C.POINTER(abi.rt_stats)]
@@ -156,6 +158,13 @@ class OracleScene:
         st = abi.rt_stats()
         obj = lib().oracle_trace(self.h, op, dpp, tnear, C.byref(t), C.byref(tri), C.byref(st))
         return obj, t.value, tri.value, Stats.from_c(st)
+
+    def hit_normal(self, orig, dir, obj, t, tri):
+        """shade's hitNormal for the hit trace() reported (xyz, not renormalised)."""
+        (oa, op), (da, dpp) = _dp(orig), _dp(dir)
+        out = (C.c_double * 3)()
+        lib().oracle_hit_normal(self.h, op, dpp, int(obj), float(t), int(tri), out)
+        return np.array(list(out))
 
     def calc_pixel(self, opts: Options, x, y):
         o = opts.to_c()

@@ -601,6 +601,18 @@ static shading_info shading_info_for(const rt_light_desc *l, v4 p) {
   return si;
 }
 
+/* hitNormal (renderer.nim:79-88): objectToWorld * normal(hitO), or
+ * objectToWorld * normals[face] for a mesh hit; not renormalised. */
+static v4 hit_normal(const oracle_scene *s, const rt_object_desc *ob, v4 hit_w, int64_t tri_hit) {
+  if (tri_hit < 0) {
+    const v4 hit_o = mat_mul_v4(ob->world_to_object, hit_w);
+    return mat_mul_v4(ob->object_to_world, object_normal(ob, hit_o));
+  }
+  const double *fn = &s->meshes[ob->mesh].normals[3 * tri_hit];
+  const v4 nrm = {fn[0], fn[1], fn[2], 0.0};
+  return mat_mul_v4(ob->object_to_world, nrm);
+}
+
 /* shade (renderer.nim:71-127) with shadeDiffuse (shader.nim:12-17). */
 static void shade(const oracle_scene *s, const rt_options *o, ray_t *ray, int32_t obj,
                   double t_hit, double out[3], rt_stats *st) {
@@ -610,15 +622,7 @@ static void shade(const oracle_scene *s, const rt_options *o, ray_t *ray, int32_
   }
   const rt_object_desc *ob = &s->objects[obj];
   const v4 hit_w = v4_add(ray->orig, v4_scale(ray->dir, t_hit));
-  const v4 hit_o = mat_mul_v4(ob->world_to_object, hit_w);
-  v4 n;
-  if (ray->tri_hit < 0) {
-    n = mat_mul_v4(ob->object_to_world, object_normal(ob, hit_o));
-  } else {
-    const double *fn = &s->meshes[ob->mesh].normals[3 * ray->tri_hit];
-    const v4 nrm = {fn[0], fn[1], fn[2], 0.0};
-    n = mat_mul_v4(ob->object_to_world, nrm);
-  }
+  const v4 n = hit_normal(s, ob, hit_w, ray->tri_hit);
   double res[3] = {0.0, 0.0, 0.0};
   for (int32_t li = 0; li < s->nlight; ++li) {
     const shading_info si = shading_info_for(&s->lights[li], hit_w);
@@ -948,6 +952,14 @@ int32_t oracle_trace(const oracle_scene *s, const double orig[4], const double d
   const int32_t obj = trace(s, &r, t_near, t_hit, stats ? stats : &local);
   if (tri_hit) *tri_hit = r.tri_hit;
   return obj;
+}
+
+void oracle_hit_normal(const oracle_scene *s, const double orig[4], const double dir[4],
+                       int32_t obj, double t_hit, int64_t tri_hit, double out[3]) {
+  const v4 o = {orig[0], orig[1], orig[2], orig[3]};
+  const v4 d = {dir[0], dir[1], dir[2], dir[3]};
+  const v4 n = hit_normal(s, &s->objects[obj], v4_add(o, v4_scale(d, t_hit)), tri_hit);
+  out[0] = n.x; out[1] = n.y; out[2] = n.z;
 }
 
 /* linearToSRGB (color.nim:17-22) + writePpm.outvalue (framebuf.nim:74-78). */

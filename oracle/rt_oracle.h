@@ -60,6 +60,11 @@ double oracle_sphere_intersect(double r, const double orig[4],
 int32_t oracle_trace(const oracle_scene *s, const double orig[4],
                      const double dir[4], double t_near, double *t_hit,
                      int64_t *tri_hit, rt_stats *stats);
+/* shade's hitNormal (renderer.nim:79-88) for the hit oracle_trace reported:
+ * objectToWorld * normal, not renormalised. */
+void oracle_hit_normal(const oracle_scene *s, const double orig[4],
+                       const double dir[4], int32_t obj, double t_hit,
+                       int64_t tri_hit, double out[3]);
 /* The (m, m) sample table of a stochastic antialias kind for pixel (x, y):
  * sx/sy hold m*m offsets in the reference's p[j*m + i] order. */
 void oracle_sample_table(int32_t kind, int32_t m, uint64_t seed, int32_t x,
