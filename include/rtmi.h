@@ -687,6 +687,62 @@ int rt_pick_pixels(rt_scene *scene, const rt_options *opts, int64_t n,
                    const double *xy, uint32_t flags, rt_hit *hits,
                    double *normals, rt_stats *out);
 
+/* ---- radiance queries ---------------------------------------------------
+ * shade (renderer.nim:71-127) itself — "what colour does this ray see" — for
+ * batches of caller-supplied rays: an orthographic, panoramic, stereo or
+ * thin-lens camera with its own samples, a light probe or cube map at a
+ * point, radiance baked at surface points, a preview of what a mirror shows.
+ * The caller forms the rays; the library answers with the reference's colour,
+ * float64 operation for operation (there is no float32 mode).
+ *
+ * Ray i is initRay(orig_i, dir_i) (geom.nim:41-48) with depth 1; dir is taken
+ * as given, NOT normalised, as in rt_trace_rays. Its colour is
+ * shade(ray, trace(ray, scene.objects, +inf)) (renderer.nim:47-127): hitNormal,
+ * getShadingInfo, one shadow ray per light, shadeDiffuse and the reflection
+ * recursion — what calcPixelNoSampling computes once castPrimaryRay has
+ * formed the ray. A miss gives bgColor. The scene's camera is not read.
+ *  - opts: only bias, max_ray_depth and precision are read (width, height
+ *    and antialias are ignored). precision must be RT_FP64 (RT_FP32 is
+ *    RT_E_UNSUPPORTED); with reflective materials max_ray_depth above 7 is
+ *    RT_E_UNSUPPORTED, as for a render.
+ *  - group >= 1 and n % group == 0, else RT_E_INVALID; the outputs hold
+ *    n / group colours. group == 1: output i is ray i's colour as computed
+ *    (no sum and no multiply: a -0.0 stays -0.0). group > 1: output k is
+ *    calcPixel's expression (renderer.nim:147-159) over rays k*group ..
+ *    k*group + group - 1: from vec3(0), the colours added in index order,
+ *    then one multiplication by 1.0 / group.
+ *  - rgb: float64, three per colour. rgb32: the same values converted to
+ *    float32 as Framebuf stores them, so a custom-camera image can go
+ *    straight to rt_ppm_encode_device / rt_rgba_encode_device. Either may be
+ *    NULL; both NULL with n > 0 is RT_E_INVALID.
+ *  - A degenerate ray — a non-finite component or an all-zero direction —
+ *    has the colour (0, 0, 0) and adds nothing to the Stats; it contributes
+ *    +0 to its group's sum, and the group still divides by `group`.
+ *  - out (may be NULL) receives all five fields: num_primary_rays is the
+ *    number of rays that are not degenerate; tests, hits, shadow rays and
+ *    reflection rays as the reference counts them. A _device call with
+ *    out == NULL only enqueues work on hip_stream; with out it waits.
+ *  - flags: RT_QUERY_SORT traces the rays in rt_trace_rays' coherence order;
+ *    outputs and Stats are the same byte for byte. RT_QUERY_ANY_HIT and
+ *    unknown bits are RT_E_INVALID.
+ * Locking and ordering are the ray queries': the call takes the scene's
+ * lock, runs after a render or query still in flight on the scene, sees the
+ * scene as the last rt_scene_set_lights / _set_objects / _set_mesh_vertices
+ * left it, and leaves everything rt_scene_last_* reports the last render
+ * call's. n == 0 is RT_OK and launches nothing; n < 0 and null required
+ * pointers are RT_E_INVALID; n >= 2^31 is RT_E_UNSUPPORTED. */
+
+/* Device form: d_orig / d_dir (n*3 doubles), d_rgb (n/group*3 doubles or
+ * NULL) and d_rgb32 (n/group*3 floats or NULL) are device memory. */
+int rt_shade_rays_device(rt_scene *scene, const rt_options *opts, int64_t n,
+                         const double *d_orig, const double *d_dir, int32_t group,
+                         uint32_t flags, double *d_rgb, float *d_rgb32,
+                         void *hip_stream, rt_stats *out);
+/* Host form: the same arrays in caller memory; returns with the answers. */
+int rt_shade_rays(rt_scene *scene, const rt_options *opts, int64_t n,
+                  const double *orig, const double *dir, int32_t group,
+                  uint32_t flags, double *rgb, float *rgb32, rt_stats *out);
+
 /* ---- helpers ----------------------------------------------------------- */
 
 /* glm-style inverse of a column-major 4x4 (what geom.nim's

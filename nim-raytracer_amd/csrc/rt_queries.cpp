@@ -1,5 +1,7 @@
 // rt_queries.cpp — ray queries (rt_trace_rays* / rt_pick_pixels*): float64
-// closest hit, any hit and pixel picking on a scene, beside its render calls.
+// closest hit, any hit and pixel picking on a scene, beside its render calls;
+// and radiance queries (rt_shade_rays*): the reference's colour along
+// caller-supplied rays.
 #include <cmath>
 #include <cstring>
 
@@ -59,56 +61,82 @@ void fill_query(const rt_scene* s, int width, int height, RenderParams<double>& 
   p.max_iters = (int32_t)std::min<int64_t>(INT32_MAX, 2 * s->num_nodes + 16);
 }
 
-// The device body of every query (the scene's lock held, its device
-// current): q's ray, hit and normal pointers are device memory.
-int query_device(rt_scene* s, const RenderParams<double>& p, QueryParams q, uint32_t flags, hipStream_t st,
-                 rt_stats* out) {
+// What every query does before its kernels (the scene's lock held, its device
+// current): orders itself after a render still in flight on the scene, and
+// after the last query (it shares this one's temporaries) unless this stream
+// orders them anyway; makes sure of the per-wave Stats rows.
+int query_begin(rt_scene* s, hipStream_t st) {
   if (!s->q_done) HIP_TRY(hipEventCreateWithFlags(&s->q_done.h, hipEventDisableTiming));
-  // after a render still in flight on the scene, and after the last query
-  // (it shares this one's temporaries) unless this stream orders them anyway
   if (st != s->done_stream) HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
   if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
   const size_t rows = (size_t)s->max_waves;
   if (s->q_partials.n < (rows + 1) * kStatSlots) {
     if (int rc = s->q_partials.alloc((rows + 1) * kStatSlots)) return rc;
   }
-  if (s->q_blocks_per_cu < 0) s->q_blocks_per_cu = rtmi_query_blocks_per_cu();
-  if (s->q_blocks_per_cu <= 0) return fail(RT_E_DEVICE, "the ray query kernel is not resident on this device");
-  q.any_hit = (flags & RT_QUERY_ANY_HIT) ? 1 : 0;
-  q.partials = s->q_partials.p;
+  return RT_OK;
+}
+
+// RT_QUERY_SORT: q.order = the batch's coherence order (nullptr without the flag)
+int query_order(rt_scene* s, QueryParams& q, uint32_t flags, hipStream_t st) {
   q.order = nullptr;
-  if (flags & RT_QUERY_SORT) {
-    const size_t need = rtmi_query_sort_bytes(q.n);
-    if (!need) return fail(RT_E_DEVICE, "sizing the ray sort failed");
-    if (s->q_sort.n < need) {
-      // an earlier query may still read the old buffer
-      if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
-      if (int rc = s->q_sort.alloc(need)) return rc;
-    }
-    QuerySortBufs b;
-    rtmi_query_sort_carve(s->q_sort.p, q.n, &b);
-    if (const int e = rtmi_query_sort(&q, &b, st))
-      return fail(RT_E_DEVICE, "ray sort failed: %s", hipGetErrorString((hipError_t)e));
-    q.order = b.idx2;
+  if (!(flags & RT_QUERY_SORT)) return RT_OK;
+  const size_t need = rtmi_query_sort_bytes(q.n);
+  if (!need) return fail(RT_E_DEVICE, "sizing the ray sort failed");
+  if (s->q_sort.n < need) {
+    // an earlier query may still read the old buffer
+    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+    if (int rc = s->q_sort.alloc(need)) return rc;
   }
-  // the grid: the device's resident blocks, or fewer when the batch is small
-  const long long steps = (q.n + 63) / 64;
-  const int blocks = (int)std::max(1LL, std::min({(steps + 3) / 4, (long long)s->q_blocks_per_cu * s->num_cus,
-                                                  (long long)s->max_waves / 4}));
-  if (const int e = rtmi_launch_query(&p, &q, blocks, st))
-    return fail(RT_E_DEVICE, "ray query launch failed: %s", hipGetErrorString((hipError_t)e));
-  unsigned long long* acc = s->q_partials.p + rows * kStatSlots;
-  if (out) {
+  QuerySortBufs b;
+  rtmi_query_sort_carve(s->q_sort.p, q.n, &b);
+  if (const int e = rtmi_query_sort(&q, &b, st))
+    return fail(RT_E_DEVICE, "ray sort failed: %s", hipGetErrorString((hipError_t)e));
+  q.order = b.idx2;
+  return RT_OK;
+}
+
+// the grid: the device's resident blocks, or fewer when the batch is small
+int query_blocks(const rt_scene* s, long long n, int blocks_per_cu) {
+  const long long steps = (n + 63) / 64;
+  return (int)std::max(1LL, std::min({(steps + 3) / 4, (long long)blocks_per_cu * s->num_cus,
+                                      (long long)s->max_waves / 4}));
+}
+
+// After a query's kernels: the Stats rows of its `blocks` blocks summed (when
+// the caller reads them: h receives the kStatSlots sums, after a wait), and
+// the query's completion recorded.
+int query_end(rt_scene* s, int blocks, hipStream_t st, unsigned long long* h) {
+  unsigned long long* acc = s->q_partials.p + (size_t)s->max_waves * kStatSlots;
+  if (h) {
     if (const int e = rtmi_launch_query_reduce(s->q_partials.p, blocks * 4, acc, st))
       return fail(RT_E_DEVICE, "ray query stats reduction failed: %s", hipGetErrorString((hipError_t)e));
   }
   HIP_TRY(hipEventRecord(s->q_done, st));
   s->q_done_rec = true;
   s->q_stream = st;
-  if (out) {
-    unsigned long long h[kStatSlots];
-    HIP_TRY(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, st));
+  if (h) {
+    HIP_TRY(hipMemcpyAsync(h, acc, kStatSlots * sizeof *h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+  }
+  return RT_OK;
+}
+
+// The device body of every hit query (the scene's lock held, its device
+// current): q's ray, hit and normal pointers are device memory.
+int query_device(rt_scene* s, const RenderParams<double>& p, QueryParams q, uint32_t flags, hipStream_t st,
+                 rt_stats* out) {
+  if (int rc = query_begin(s, st)) return rc;
+  if (s->q_blocks_per_cu < 0) s->q_blocks_per_cu = rtmi_query_blocks_per_cu();
+  if (s->q_blocks_per_cu <= 0) return fail(RT_E_DEVICE, "the ray query kernel is not resident on this device");
+  q.any_hit = (flags & RT_QUERY_ANY_HIT) ? 1 : 0;
+  q.partials = s->q_partials.p;
+  if (int rc = query_order(s, q, flags, st)) return rc;
+  const int blocks = query_blocks(s, q.n, s->q_blocks_per_cu);
+  if (const int e = rtmi_launch_query(&p, &q, blocks, st))
+    return fail(RT_E_DEVICE, "ray query launch failed: %s", hipGetErrorString((hipError_t)e));
+  unsigned long long h[kStatSlots];
+  if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
+  if (out) {
     *out = rt_stats{};
     out->num_primary_rays = q.xy ? h[STAT_PRIMARY] : 0;  // camera rays are a pick's; the kernel counts the rays it traced
     out->num_intersection_tests = h[STAT_TESTS];
@@ -240,4 +268,134 @@ extern "C" int rt_pick_pixels(rt_scene* s, const rt_options* o, int64_t n, const
   const void* const in[4] = {nullptr, nullptr, nullptr, xy};
   const size_t bytes[4] = {0, 0, 0, (size_t)n * 2 * sizeof(double)};
   return query_host(s, p, n, in, bytes, flags, hits, normals, out);
+}
+
+// ---- radiance queries (rt_shade_rays*) --------------------------------------
+namespace {
+
+// What both shade entry points check before they take the scene's lock.
+int shade_check(const rt_scene* s, const rt_options* o, int64_t n, int32_t group, uint32_t flags, const void* rgb,
+                const void* rgb32) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!o) return fail(RT_E_INVALID, "null options");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (flags & ~(uint32_t)RT_QUERY_SORT)
+    return fail(RT_E_INVALID, "rt_shade_rays takes RT_QUERY_SORT only (flags 0x%x)", flags);
+  if (group < 1) return fail(RT_E_INVALID, "group %d (at least 1)", group);
+  if (n % group) return fail(RT_E_INVALID, "%lld rays are not a whole number of groups of %d", (long long)n, group);
+  if (n > 0 && !rgb && !rgb32) return fail(RT_E_INVALID, "null rgb and rgb32");
+  if (o->precision != RT_FP64)
+    return fail(o->precision == RT_FP32 ? RT_E_UNSUPPORTED : RT_E_INVALID,
+                "radiance queries are float64 only (precision %d)", o->precision);
+  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
+  return RT_OK;
+}
+
+// The device body of both forms (the scene's lock held, its device current):
+// q.orig / q.dir and the outputs are device memory.
+int shade_device(rt_scene* s, const rt_options* o, QueryParams q, int32_t group, uint32_t flags, double* d_rgb,
+                 float* d_rgb32, hipStream_t st, rt_stats* out) {
+  // as check_options says it for a render (any_reflective: under the lock, rt_scene_set_objects may flip it)
+  if (s->any_reflective && o->max_ray_depth > kMaxShadeLevels - 1)
+    return fail(RT_E_UNSUPPORTED, "max_ray_depth %d > %d with reflective materials", o->max_ray_depth,
+                kMaxShadeLevels - 1);
+  RenderParams<double> p;
+  fill_query(s, 1, 1, p);
+  p.bias = o->bias;
+  p.max_depth = o->max_ray_depth;
+  if (int rc = query_begin(s, st)) return rc;
+  // one level when no reflection ray can follow a hit (renderer.nim:104)
+  const int reflective = s->any_reflective && o->max_ray_depth >= 1 ? 1 : 0;
+  int& bpc = s->q_shade_blocks_per_cu[reflective];
+  if (bpc < 0) bpc = rtmi_shade_blocks_per_cu(reflective);
+  if (bpc <= 0) return fail(RT_E_DEVICE, "the radiance query kernel is not resident on this device");
+  ShadeOut so{d_rgb, d_rgb32};
+  if (group > 1) {
+    // the rays' colours, summed per group by k_shade_reduce
+    const size_t need = (size_t)q.n * 3;
+    if (s->q_shade.n < need) {
+      if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));  // an earlier query may still read the old buffer
+      if (int rc = s->q_shade.alloc(need)) return rc;
+    }
+    so = ShadeOut{s->q_shade.p, nullptr};
+  }
+  q.partials = s->q_partials.p;
+  if (int rc = query_order(s, q, flags, st)) return rc;
+  const int blocks = query_blocks(s, q.n, bpc);
+  if (const int e = rtmi_launch_shade(&p, &q, &so, reflective, blocks, st))
+    return fail(RT_E_DEVICE, "radiance query launch failed: %s", hipGetErrorString((hipError_t)e));
+  if (group > 1) {
+    if (const int e = rtmi_launch_shade_reduce(so.rgb, q.n / group, group, 1.0 / (double)group, d_rgb, d_rgb32, st))
+      return fail(RT_E_DEVICE, "radiance query group sum failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  unsigned long long h[kStatSlots];
+  if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
+  if (out) {
+    out->num_primary_rays = h[STAT_PRIMARY];
+    out->num_intersection_tests = h[STAT_TESTS];
+    out->num_intersection_hits = h[STAT_HITS];
+    out->num_shadow_rays = h[STAT_SHADOW];
+    out->num_reflection_rays = h[STAT_REFL];
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_shade_rays_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_orig,
+                                    const double* d_dir, int32_t group, uint32_t flags, double* d_rgb, float* d_rgb32,
+                                    void* stream, rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, d_rgb, d_rgb32)) return rc;
+  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  QueryParams q{};
+  q.orig = d_orig;
+  q.dir = d_dir;
+  q.n = n;
+  return shade_device(s, o, q, group, flags, d_rgb, d_rgb32, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_shade_rays(rt_scene* s, const rt_options* o, int64_t n, const double* orig, const double* dir,
+                             int32_t group, uint32_t flags, double* rgb, float* rgb32, rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, rgb, rgb32)) return rc;
+  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  // the batch copied into the scene's staging buffer, shaded on the scene's
+  // own stream, the colours copied back (query_host's discipline)
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t v3 = (size_t)n * 3 * sizeof(double), ng = (size_t)(n / group);
+  const size_t off_dir = al(v3), off_rgb = off_dir + al(v3);
+  const size_t off_rgb32 = off_rgb + (rgb ? al(ng * 3 * sizeof(double)) : 0);
+  const size_t total = off_rgb32 + (rgb32 ? al(ng * 3 * sizeof(float)) : 0);
+  hipStream_t st = s->stream;
+  if (s->q_stage.n < total) {
+    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+    if (int rc = s->q_stage.alloc(total)) return rc;
+  }
+  unsigned char* base = s->q_stage.p;
+  // the staging buffer's last user was a query on this stream, or has been waited for
+  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
+  HIP_TRY(hipMemcpyAsync(base, orig, v3, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(base + off_dir, dir, v3, hipMemcpyHostToDevice, st));
+  QueryParams q{};
+  q.orig = (const double*)base;
+  q.dir = (const double*)(base + off_dir);
+  q.n = n;
+  double* d_rgb = rgb ? (double*)(base + off_rgb) : nullptr;
+  float* d_rgb32 = rgb32 ? (float*)(base + off_rgb32) : nullptr;
+  if (int rc = shade_device(s, o, q, group, flags, d_rgb, d_rgb32, st, out)) return rc;
+  if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (rgb32) HIP_TRY(hipMemcpyAsync(rgb32, d_rgb32, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return RT_OK;
 }

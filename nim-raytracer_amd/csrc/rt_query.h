@@ -1,6 +1,6 @@
-// rt_query.h — ray queries (include/rtmi.h rt_trace_rays* / rt_pick_pixels*):
-// what the host library (rt_queries.cpp) and the query kernels
-// (rt_kernels_query.hip) share.
+// rt_query.h — ray queries (include/rtmi.h rt_trace_rays* / rt_pick_pixels* /
+// rt_shade_rays*): what the host library (rt_queries.cpp) and the query
+// kernels (rt_kernels_query.hip, rt_kernels_shade.hip) share.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -33,6 +33,14 @@ struct QueryParams {
   int32_t pad;
 };
 
+// Where k_shade_rays leaves ray i's colour (rt_shade_rays*): three float64 at
+// rgb[3 i] and / or three float32 at rgb32[3 i] (device memory; nullptr: not
+// written). A call with group > 1 points rgb at a temporary k_shade_reduce sums.
+struct ShadeOut {
+  double* rgb;
+  float* rgb32;
+};
+
 // RT_QUERY_SORT's device temporaries, carved from one allocation of
 // rtmi_query_sort_bytes(n) bytes: keys and ray indices (in and out of the
 // radix sort), the batch's bounds, rocPRIM's temporary storage.
@@ -57,4 +65,12 @@ void rtmi_query_sort_carve(void* base, long long n, rtmi::QuerySortBufs* out);
 // keys of the batch (q.orig / q.dir / q.tnear, or q.xy) and the sorted ray
 // order at b.idx2
 int rtmi_query_sort(const rtmi::QueryParams* q, const rtmi::QuerySortBufs* b, void* stream);
+// k_shade_rays (rt_kernels_shade.hip): reflective = 0: the one-level
+// instantiation, 1: kMaxShadeLevels. Resident blocks per CU, and the launch.
+int rtmi_shade_blocks_per_cu(int reflective);
+int rtmi_launch_shade(const rtmi::RenderParams<double>* p, const rtmi::QueryParams* q, const rtmi::ShadeOut* so,
+                      int reflective, int blocks, void* stream);
+// calcPixel's sum over each run of `group` ray colours: ngroups outputs
+int rtmi_launch_shade_reduce(const double* ray_rgb, long long ngroups, int group, double inv_len, double* rgb,
+                             float* rgb32, void* stream);
 }

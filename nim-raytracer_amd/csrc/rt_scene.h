@@ -262,7 +262,7 @@ struct rt_scene {
   double objgrid_ms = 0.0;         // the last build's object-grid pass, wall time
   DevBuf<DevObjBox> objbox_dev;
   DevBuf<float> fb_scratch;
-  // ray queries (rt_trace_rays* / rt_pick_pixels*): buffers of their own, so a
+  // ray queries (rt_trace_rays* / rt_pick_pixels* / rt_shade_rays*): buffers of their own, so a
   // query leaves the last render call's rows, Stats and lists as they are.
   // Allocated by the first query that needs them, grown on demand (after
   // waiting for the queries that use them), released with the scene.
@@ -273,6 +273,10 @@ struct rt_scene {
   hipStream_t q_stream = nullptr;
   bool q_done_rec = false;
   int q_blocks_per_cu = -1;               // k_trace_rays' resident blocks per CU
+  // radiance queries (rt_shade_rays*) share all of the above, under the same
+  // event discipline, and add:
+  DevBuf<double> q_shade;                 // group > 1: the batch's per-ray colours (n * 3)
+  int q_shade_blocks_per_cu[2] = {-1, -1};  // k_shade_rays' resident blocks per CU: one level, kMaxShadeLevels
   int max_waves = 0;
   int64_t num_triangles = 0, num_nodes = 0;
   int max_depth = 0;
@@ -288,7 +292,7 @@ struct rt_scene {
                queue2.bytes() + f64_tables.bytes() + refl_queue.bytes() + refl_sec.bytes() + fb_scratch.bytes() +
                grids.bytes() + grid_off.bytes() + grid_ent.bytes() + obj_grids.bytes() + obj_grid_mask.bytes() +
                bin_dev.bytes() + sat_dev.bytes() + objbox_dev.bytes() + lrec.bytes() + grec.bytes() + fr.bytes() +
-               fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + refit_parent.bytes() +
+               fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + q_shade.bytes() + refit_parent.bytes() +
                refit_arrivals.bytes() + mesh_scratch.bytes();
     for (const MeshKeep& k : mesh_keep) b += k.verts.bytes() + k.faces.bytes() + k.order.bytes();
     for (const std::unique_ptr<Order>& o : orders) b += o->cost.bytes() + o->perm.bytes();

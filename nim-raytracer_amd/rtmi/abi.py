@@ -246,6 +246,11 @@ SIGNATURES = {
                                         C.POINTER(rt_stats)]),
     "rt_pick_pixels": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_double), C.c_uint32,
                                  C.POINTER(rt_hit), C.POINTER(C.c_double), C.POINTER(rt_stats)]),
+    "rt_shade_rays_device": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, _P, _P, C.c_int32, C.c_uint32, _P, _P,
+                                       _P, C.POINTER(rt_stats)]),
+    "rt_shade_rays": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                C.c_int32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                C.POINTER(rt_stats)]),
 }
 
 

@@ -213,6 +213,47 @@ class DeviceScene:
         return self._query_device(xy, n, flags, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_device(
             self.h, C.byref(o), n, C.c_void_p(xy.data_ptr()), flags, hits, nrm, _stream(stream), st))
 
+    # -- radiance queries (rt_shade_rays*) -----------------------------------
+    def shade_rays(self, opts: Options, orig, dir, group=1, sort=False, f32=False, stats=False, stream=None):
+        """shade(ray, trace(ray)) (renderer.nim:47-127) for n caller-supplied
+        rays — the reference's colour along each, whatever camera formed it;
+        the scene's own camera is not read. orig and dir are (n, 3) float64,
+        numpy arrays (the host form) or CUDA torch tensors (the device form,
+        enqueued on `stream`; it waits only with stats=True); dir as given,
+        not normalised. Of opts only bias, maxRayDepth and precision (fp64)
+        are read. group=1: one colour per ray; group=g: calcPixel's mean of
+        each run of g rays, summed in index order. Returns rgb as an
+        (n / group, 3) array of the same kind, float64 or (f32=True) float32
+        as Framebuf stores it, then the Stats when asked. A degenerate ray
+        (a non-finite component, a zero direction) is (0, 0, 0) and counts
+        nowhere; sort traces the rays in a coherence order (the same answers)."""
+        flags = abi.RT_QUERY_SORT if sort else 0
+        group = int(group)
+        o = opts.to_c()
+        st = abi.rt_stats()
+        pst = C.byref(st) if stats else None
+        if _is_host(orig):
+            og, d = _host_f64(orig, (-1, 3)), _host_f64(dir, (-1, 3))
+            n = og.shape[0]
+            if d.shape[0] != n:
+                raise ValueError("orig and dir must hold the same number of rays")
+            ng = n // group if group >= 1 and n % group == 0 else 0  # (the library reports a bad group)
+            rgb = np.zeros((ng, 3), dtype=np.float32 if f32 else np.float64)
+            check(lib().rt_shade_rays(self.h, C.byref(o), n, _dptr(og), _dptr(d), group, flags,
+                                      None if f32 else _dptr(rgb),
+                                      rgb.ctypes.data_as(C.POINTER(C.c_float)) if f32 else None, pst))
+            return (rgb, Stats.from_c(st)) if stats else rgb
+        import torch
+        n = _dev_f64(orig, None, 3)
+        _dev_f64(dir, n, 3)
+        ng = n // group if group >= 1 and n % group == 0 else 0
+        rgb = torch.empty((ng, 3), dtype=torch.float32 if f32 else torch.float64, device=orig.device)
+        p = C.c_void_p(rgb.data_ptr())
+        check(lib().rt_shade_rays_device(self.h, C.byref(o), n, C.c_void_p(orig.data_ptr()),
+                                         C.c_void_p(dir.data_ptr()), group, flags, None if f32 else p,
+                                         p if f32 else None, _stream(stream), pst))
+        return (rgb, Stats.from_c(st)) if stats else rgb
+
     def _query_host(self, n, flags, normals, stats, call):
         hits = np.zeros(n, dtype=_HIT_DTYPE)
         nrm = np.zeros((n, 3), dtype=np.float64) if normals else None
