@@ -588,8 +588,8 @@ int rt_scene_last_batch(rt_scene *scene, int64_t *batched_groups, int64_t *fallb
  * batched kernel, RT_FLAG_NO_GEN1); 3 in both: the merged one-plane kernel
  * (RT_FLAG_NO_MIX); bit 4: reflected rays compacted per wave (reflective
  * scenes, RT_FLAG_COMPACT); bits 8-15: lanes per lean pixel of a two-class
- * call (4 or 16 for the one-plane lean kernels, 64 for one pixel per wave;
- * 0 otherwise) — mask with 0x1f to compare the kernel kinds. Host-side
+ * call (4 or 16 for the one-plane lean kernel, kind 2 or 3; 64, one pixel
+ * per wave, only with the general lean kernel, kind 1; 0 otherwise) — mask with 0x1f to compare the kernel kinds. Host-side
  * bookkeeping, no wait. */
 int rt_scene_last_lean_kernel(rt_scene *scene, int32_t *kind);
 /* Of the last render call's lean pixel groups (rt_scene_last_split counts

@@ -394,6 +394,10 @@ enum : unsigned {
   SUB_SPHERE = 1u, SUB_BOX = 2u, SUB_MESH = 4u, SUB_XF_GENERAL = 8u, SUB_POINT = 16u, SUB_REFLECT = 32u,
   SUB_STOCHASTIC = 64u
 };
+// the float32 kernel families of a feature subset: every subset has the
+// render kernel, some the lean / batched general pair or the
+// reflection-compacting kernel (rt_kernels_f32_part.hip)
+enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3 };
 // float32 kernel work queue: 64 head words, 128 B apart, zeroed per launch
 constexpr int kQueueShards = 64, kQueueStride = 32;
 // object-binned batches (k_render_fast, analytic scenes with distant lights,
@@ -426,7 +430,6 @@ int rtmi_launch_lean_f32(const rtmi::FastParams* p, unsigned subset, int blocks,
 int rtmi_lean_f32_blocks_per_cu(unsigned subset, size_t shmem);
 int rtmi_launch_lean1_f32(const rtmi::FastParams* p, int nl, int lp, int blocks, void* stream);
 int rtmi_lean1_f32_blocks_per_cu(int nl, int lp);
-int rtmi_lean1_quads();
 int rtmi_launch_gen1_f32(const rtmi::FastParams* p, int nl, int blocks, void* stream);
 int rtmi_gen1_f32_blocks_per_cu(int nl);
 int rtmi_launch_mix1_f32(const rtmi::FastParams* p, int nl, int lp, int blocks, void* stream);

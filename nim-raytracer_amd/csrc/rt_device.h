@@ -1229,13 +1229,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEVELS > 1 
         ws.v[STAT_PRIMARY] += popc32(ballot(sv));
         V3<R> c;
         const bool lean_px = lean_need != 0u && (pinfo & (kPixCount | lean_need)) == lean_need;
-#if defined(RTMI_DIAG) && defined(RTMI_PX64_ONLY)
-        // diagnostic builds (tools/build_variant.sh): 1 = lean samples only,
-        // 2 = general samples only — a time split, wrong images on purpose
-        if (lean_px != (RTMI_PX64_ONLY == 1)) {
-          c = V3<R>{R(0), R(0), R(0)};
-        } else
-#endif
         if (lean_px)
           c = px64_lean_sample(rparams<R>(), o, d, sv, ws, cch);
         else

@@ -73,9 +73,6 @@ __device__ __forceinline__ unsigned long long bal(bool p) { return __builtin_amd
 // mask back to a per-lane predicate (llvm.amdgcn.inverse.ballot): a ballot of
 // a compound bool otherwise materialises it in a VGPR (v_cndmask 0/1 +
 // v_cmp_ne) before the popcount.
-#ifndef RTMI_FCMP_MASKS
-#define RTMI_FCMP_MASKS 1
-#endif
 __device__ __forceinline__ unsigned long long m_ge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 3); }
 __device__ __forceinline__ unsigned long long m_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 4); }
 __device__ __forceinline__ bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
@@ -291,13 +288,10 @@ __device__ __forceinline__ const char* lrec_of(KP p, int light) {
   return (const char*)(p->lrec_base + (uint64_t)light * (uint64_t)p->lrec_stride);
 }
 
-#ifndef RTMI_GRID_REC
-#define RTMI_GRID_REC 1
-#endif
 // The cell-ordered records of a light's grid, aligned with its entries
-// (p->grid_ent + G.ent_base): list_search_batch's lb under RTMI_GRID_REC.
+// (p->grid_ent + G.ent_base): list_search_batch's lb.
 __device__ __forceinline__ const char* grid_rec_of(KP p, int light, const LightGrid& G) {
-  return RTMI_GRID_REC ? (const char*)(p->grid_rec + G.ent_base) : lrec_of(p, light);
+  return (const char*)(p->grid_rec + G.ent_base);
 }
 
 // A record of the float32 tree (FastParams.tree) at a byte offset: one scalar
@@ -464,9 +458,6 @@ __device__ __forceinline__ void list_search(KP p, const int32_t* ent, int b, int
     ws.v[STAT_TRI_FETCH] += (unsigned int)(e - b);
     ws.v[STAT_LANE_TRIS] += pc(bal(tc >= 0.0f)) * (unsigned int)(e - b);
   }
-#ifdef RTMI_DIAG_NOLIST
-  return;  // diagnostic build only: the binned searches' share of the frame
-#endif
   auto test = [&](int off) {
     if (lb) ltri_test(load_ltri((const RT_CONST LTri*)(lb + (unsigned)off)), o, key, tc);
     else tri_test(load_tri(rec<TriFast>(p, off)), o, d, key, tc);
@@ -515,11 +506,6 @@ __device__ __forceinline__ float analytic_t(KP p, const FObj& ob, int i, F3 o, F
 template <unsigned F, int S, class Body>
 __device__ __forceinline__ void analytic_t_batch(KP p, const FObj& ob, int i, const F3 (&o)[S], const F3 (&d)[S],
                                                  Body&& body) {
-#ifdef RTMI_PER_RAY_DISPATCH  // diagnostic A/B: the dispatch per ray
-#pragma unroll
-  for (int k = 0; k < S; ++k) body(k, analytic_t<F>(p, ob, i, o[k], d[k]));
-  return;
-#endif
   auto cases = [&](auto general) {
     constexpr bool G = decltype(general)::value;
     auto xform = [&](int k, F3& ro, F3& rd) {
@@ -666,9 +652,7 @@ __device__ __forceinline__ Hit trace(KP p, F3 o, F3 d, float tmax, bool active, 
   RT_STAMP(t_trace0);
   Hit h{-1, -1, tmax};
   const bool early = (F & F_MESH) && shadow && p->shadow_mesh >= 0;
-#if RTMI_FCMP_MASKS
   const unsigned long long actm = bal(active);
-#endif
   // Object bins (scenes of 4..64 objects, rt_bins.h): the objects the wave's
   // bins list, in scene order; an object no bin lists cannot be hit (it
   // would add nothing to the closest hit or the hit count). Up to 4 distinct
@@ -774,14 +758,9 @@ __device__ __forceinline__ Hit trace(KP p, F3 o, F3 d, float tmax, bool active, 
       }
     }
     if ((F & F_REFLECT) && i == src) t = -finf();
-#if RTMI_FCMP_MASKS
     const unsigned long long um = m_ge(t, 0.0f) & m_lt(t, h.t) & actm;
     ws.v[STAT_HITS] += pc(um);
     const bool upd = lane_in(um);
-#else
-    const bool upd = active && t >= 0.0f && t < h.t;
-    ws.v[STAT_HITS] += pc(bal(upd));
-#endif
     if (upd) {
       h.t = t;
       h.obj = i;
@@ -1071,10 +1050,6 @@ __device__ __forceinline__ void shade_path(KP p, F3 o, F3 d, bool active, int pi
   }
 }
 
-#ifndef RTMI_QUEUE_AHEAD
-#define RTMI_QUEUE_AHEAD 1
-#endif
-
 // Occupancy target (k_render_fast, k_render_wave). Fewer resident waves
 // buy registers: the instances whose loops spilled at 8 waves/SIMD run at 5
 // (<= 96 VGPRs): meshes with point lights or reflection (mesh-mix 1080p/64
@@ -1187,7 +1162,7 @@ __device__ __forceinline__ GroupPix group_pixel(KP p, int g, int lane) {
 // column / row as the reference's own formula gives there. Every FMA is
 // explicit, so all instances of the sample loop round alike. The cx terms
 // are innermost: a lane whose samples share a column (akGrid, m | 64) forms
-// them once per pixel (k_render_lean1) with the same roundings.
+// them once per pixel (lean1q_loop) with the same roundings.
 __device__ __forceinline__ F3 camera_ray_dir(KP p, float px, float py) {
   const float cx = (px - p->cam_b) * p->cam_a;
   const float cy = (p->cam_d - py) * p->cam_c;
@@ -1363,16 +1338,9 @@ __device__ __forceinline__ void batch_dirs(KP p, const GroupPix& gp, int it0, co
 // +0.0 and leaves every other value as it is. The float form is two compares
 // and a scalar AND of their lane masks per ray and object (the batches'
 // busiest pipe is the CU's one scalar unit). A sample that takes no part
-// holds lim = +0.0, below which nothing lies. RTMI_HIT_UINT=0: the float form.
-#ifndef RTMI_HIT_UINT
-#define RTMI_HIT_UINT 1
-#endif
+// holds lim = +0.0, below which nothing lies.
 __device__ __forceinline__ bool hit_below(float t, float lim) {
-#if RTMI_HIT_UINT
   return __float_as_uint(t + 0.0f) < __float_as_uint(lim);
-#else
-  return t >= 0.0f && t < lim;
-#endif
 }
 
 #ifndef RTMI_LEAN_BATCH
@@ -1385,14 +1353,10 @@ constexpr int kLeanBatch = RTMI_LEAN_BATCH;
 // only those of the light-grid cells their origins fall in — in scene order,
 // exactly as trace's object bins (an object no bin lists cannot be hit, so it
 // adds nothing to a closest hit or a hit count).
-// RTMI_OB_CELLS_JOINT (default 1): an object-binned batch walks the distinct
-// light-grid cells of all its samples' shadow origins once (up to 2 S cells,
-// then every object), not each sample's cells in turn (up to 4 each). The
+// An object-binned batch takes the light-grid cell masks of all its samples'
+// shadow origins at once (below), not each sample's cells in turn. The
 // object mask either way holds every object a shadow ray can hit, so frames
 // and Stats do not change.
-#ifndef RTMI_OB_CELLS_JOINT
-#define RTMI_OB_CELLS_JOINT 2
-#endif
 template <unsigned F, int S = kLeanBatch, bool OB = false>
 __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, const LdsF* tb, Acc& acc,
                                            Stats32& ws, unsigned long long cmask = ~0ull) {
@@ -1401,9 +1365,6 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
   // VALU (no exec-mask save / restore per sample). A masked-off term adds an
   // exact zero (fma(ci, 0, E) == E, acc + 0 == acc for the non-negative
   // sums), so values equal shade_path's branchy ones bit for bit.
-#ifdef RTMI_DIAG_NOSAMPLES
-  return;  // diagnostic build only: the work-item overhead without the samples
-#endif
   const F3 o = f3(p->cam[0], p->cam[1], p->cam[2]);
   F3 d[S];
   bool sv[S];
@@ -1420,22 +1381,17 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
 #pragma unroll
   for (int k = 0; k < S; ++k) {
     nprim += pc(bal(sv[k]));
-    th[k] = sv[k] ? finf() : (RTMI_HIT_UINT ? 0.0f : -1.0f);  // (hit_below: +0 takes no hit)
+    th[k] = sv[k] ? finf() : 0.0f;  // (hit_below: +0 takes no hit)
     hob[k] = -1;
   }
   ws.v[STAT_PRIMARY] += nprim;
   const int nobj = p->nobj, mesh = p->shadow_mesh;
-#ifndef RTMI_LEAN_NOPIN
   // the record arrays' bases pinned in SGPRs for the batch (opaque): the
   // compiler otherwise re-reads them from the kernel arguments before every
   // object / light visit, a dependent scalar load in front of the record's
   const FObj* objs = p->objs;
   const FLight* lights = p->lights;
   asm volatile("" : "+s"(objs), "+s"(lights));
-#else
-  const FObj* objs = p->objs;
-  const FLight* lights = p->lights;
-#endif
   unsigned hitl = 0u;
   // the analytic objects in scene order
   // (one loop with a skip test: two index ranges around the mesh measured
@@ -1461,9 +1417,6 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
   F3 oc[S];
 #pragma unroll
   for (int k = 0; k < S; ++k) oc[k] = o;
-#ifdef RTMI_DIAG_OB_NOCAM
-  cmask &= 1ull;  // diagnostic build only (wrong images): camera rays test object 0 alone
-#endif
   masked_objects(cmask, [&](const int i) {
     const FObj ob = at(objs, i);
     analytic_t_batch<F, S>(p, ob, i, oc, d, [&](int k, float t) {
@@ -1493,10 +1446,6 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
   constexpr bool kPlanesOnly = !(F & (F_SPHERE | F_BOX));
   int nhobj = 0;
   F3 Nu = f3(0.0f, 0.0f, 0.0f), alb_u = f3(0.0f, 0.0f, 0.0f);
-#ifdef RTMI_DIAG_OB_NONORMAL
-#pragma unroll
-  for (int k = 0; k < S; ++k) pend[k] = 0ull;  // diagnostic build only (wrong images): the normal pass's share
-#endif
   for (;;) {
     const int oi = first_pending<S>(pend, hob);
     if (oi < 0) break;
@@ -1578,7 +1527,6 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
           const RT_CONST LightGrid& G = cp(p->obj_grids)[li];
           unsigned long long m = p->obj_off_grid;
           bool every = false;
-#if RTMI_OB_CELLS_JOINT == 2
           // every lane loads its samples' cell masks (vector loads, one round
           // trip), ORed over the wave by DPP — instead of one scalar load per
           // distinct cell, each waited for in turn. No cap on the distinct
@@ -1598,66 +1546,9 @@ __device__ __forceinline__ void lean_batch(KP p, const GroupPix& gp, int it0, co
             every = every || bal(lk && !safe) != 0ull;
           }
           m |= ((unsigned long long)wave_or((unsigned)(mine >> 32)) << 32) | wave_or((unsigned)mine);
-#elif RTMI_OB_CELLS_JOINT
-          // the distinct cells of all S samples' origins, each mask loaded
-          // once (the samples of a pixel's lanes mostly share their cells:
-          // per sample the same cells were walked S times)
-          int cell[S];
-          unsigned long long todo[S], left = 0ull;
-#pragma unroll
-          for (int k = 0; k < S; ++k) {
-            const bool lk = lane_in(litm[k]);
-            const F3 q = so[k];
-            const float gu = __builtin_fmaf(q.x, G.e1[0], __builtin_fmaf(q.y, G.e1[1], q.z * G.e1[2]));
-            const float gv = __builtin_fmaf(q.x, G.e2[0], __builtin_fmaf(q.y, G.e2[1], q.z * G.e2[2]));
-            const float fu = (gu - G.u0) * G.inv_h, fv = (gv - G.v0) * G.inv_h;
-            const bool safe = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) <= G.rmax;
-            const bool on = fu >= 0.0f && fu < (float)G.gu && fv >= 0.0f && fv < (float)G.gv;
-            cell[k] = on ? (int)fv * G.gu + (int)fu : -1;
-            todo[k] = bal(lk && safe && on);
-            left |= todo[k];
-            every = every || bal(lk && !safe) != 0ull;
-          }
-          for (int it = 0; it < 2 * S && left != 0ull; ++it) {
-            int kc = 0;
-#pragma unroll
-            for (int k = S - 1; k >= 0; --k)
-              if (todo[k]) kc = __builtin_amdgcn_readlane(cell[k], (int)__builtin_ctzll(todo[k]));
-            left = 0ull;
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-              todo[k] &= ~bal(cell[k] == kc);
-              left |= todo[k];
-            }
-            m |= cp(p->obj_grid_mask)[G.off_base + kc];
-          }
-          every = every || left != 0ull;
-#else
-#pragma unroll
-          for (int k = 0; k < S; ++k) {
-            const bool lk = lane_in(litm[k]);
-            const F3 q = so[k];
-            const float gu = __builtin_fmaf(q.x, G.e1[0], __builtin_fmaf(q.y, G.e1[1], q.z * G.e1[2]));
-            const float gv = __builtin_fmaf(q.x, G.e2[0], __builtin_fmaf(q.y, G.e2[1], q.z * G.e2[2]));
-            const float fu = (gu - G.u0) * G.inv_h, fv = (gv - G.v0) * G.inv_h;
-            const bool safe = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) <= G.rmax;
-            const bool on = fu >= 0.0f && fu < (float)G.gu && fv >= 0.0f && fv < (float)G.gv;
-            const int cell = on ? (int)fv * G.gu + (int)fu : -1;
-            unsigned long long todo = bal(lk && safe && on);
-            for (int it = 0; it < 4 && todo != 0ull; ++it) {
-              const int kc = __builtin_amdgcn_readlane(cell, (int)__builtin_ctzll(todo));
-              todo &= ~bal(cell == kc);
-              m |= cp(p->obj_grid_mask)[G.off_base + kc];
-            }
-            every = every || todo != 0ull || bal(lk && !safe) != 0ull;
-          }
-#endif
           smask = every ? smask : m;
         }
       }
-#ifdef RTMI_DIAG_OB_NOSHADOW
-      smask = 0ull;  // diagnostic build only (wrong images): the shadow rays' object tests' share
-#endif
       masked_objects(smask, [&](const int i) {
         const FObj ob = at(objs, i);
         if constexpr (kPlanesOnly) {
@@ -1781,25 +1672,21 @@ __device__ __forceinline__ void ltri_test_t(const LR& L, F3 o, float& best, floa
 // searched in its turn).
 // diag (RTMI_DIAG_LANES builds, else nullptr): += the lanes still searching
 // at each face test of each flagged sample (lane occupancy of the search).
-// RTMI_LDS_STAGE (default 1; 0 for the A/B): each step's four face records
-// staged through the wave's LDS slice instead of one scalar load per record
-// (DESIGN.md "LDS staging": C3 0.912 -> 0.895 ms, C5 79.5 -> 78.4 ms).
-#ifndef RTMI_LDS_STAGE
-#define RTMI_LDS_STAGE 1
-#endif
-// Shadow searches (!KEY) test the light's LTri records at lb (lrec_of:
-// every light with a grid has them), camera searches (KEY) the TriFast
-// records of the tree. RTMI_GRID_REC (default 1): a shadow search reads the
-// records in entry order instead, lb = the cell-ordered copy aligned with
-// `ent` (grid_rec_of: entry k's record at lb + 64 k) — one load per step,
-// not the entries and then the records they name; 0 for the A/B.
+// Each step's four face records are staged through the wave's LDS slice
+// instead of one scalar load per record (DESIGN.md "LDS staging": C3 0.912
+// -> 0.895 ms, C5 79.5 -> 78.4 ms).
+// Camera searches (KEY) test the TriFast records of the tree that `ent`
+// names; shadow searches (!KEY) read the light's LTri records in entry
+// order, lb = the cell-ordered copy aligned with `ent` (grid_rec_of: entry
+// k's record at lb + 64 k) — one load per step, not the entries and then the
+// records they name.
 template <int S, bool KEY>
 __device__ __forceinline__ int list_search_batch(KP p, const int32_t* ent, int b, int e, unsigned fl,
                                                   const F3 (&ro)[S], const F3 (&rd)[S], const float (&stop)[S],
                                                   const unsigned long long (&own)[S], unsigned long long (&key)[S],
                                                   float (&best)[S], float (&tc)[S], unsigned* diag = nullptr,
                                                   const char* lb = nullptr) {
-  constexpr bool kCellRec = !KEY && RTMI_GRID_REC;
+  constexpr bool kCellRec = !KEY;
   // the record of entry k
   auto rec_at = [&](int k) -> const char* {
     return kCellRec ? lb + (size_t)(unsigned)k * sizeof(LTri) : lb + (unsigned)cp(ent)[k];
@@ -1830,33 +1717,27 @@ __device__ __forceinline__ int list_search_batch(KP p, const int32_t* ent, int b
       ++b;
     }
   }
-  // LDS staging (RTMI_LDS_STAGE, DESIGN.md "LDS staging"): the 4 face
-  // records of a step staged through the wave's LDS slice — lane 16 j + w
-  // loads dword w of record j (one coalesced vector load for all four), then
-  // every lane reads each record back as a broadcast (ds_read_b128 x 4) —
-  // instead of one scalar load per record. 1: both searches, 2: the shadow
-  // (cell list) searches only, 3: the camera (pixel list) searches only.
-  constexpr bool kStage = RTMI_LDS_STAGE == 1 || (RTMI_LDS_STAGE == 2 && !KEY) || (RTMI_LDS_STAGE == 3 && KEY);
-#if RTMI_LDS_STAGE
+  // LDS staging (DESIGN.md "LDS staging"): the 4 face records of a step
+  // staged through the wave's LDS slice — lane 16 j + w loads dword w of
+  // record j (one coalesced vector load for all four), then every lane reads
+  // each record back as a broadcast (ds_read_b128 x 4) — instead of one
+  // scalar load per record.
   __shared__ uint4 stage_lds[4][16];
   uint4* stage = stage_lds[threadIdx.x >> 6];
-#else
-  uint4* stage = nullptr;
-#endif
   for (int k0 = b; k0 < e; k0 += 4) {
     int r[4] = {0, 0, 0, 0};
     if constexpr (!kCellRec) {
       const RT_CONST int32_t* q = cp(ent) + k0;
       r[0] = q[0], r[1] = q[1], r[2] = q[2], r[3] = q[3];
     }
-    if constexpr (kStage) {
+    {
       const int lane = (int)__lane_id(), j = lane >> 4, w = lane & 15;
       if constexpr (kCellRec) {  // the step's four records are 256 contiguous bytes
         const unsigned int* src = (const unsigned int*)rec_at(k0);
         ((unsigned int*)stage)[lane] = k0 + j < e ? src[lane] : 0u;
       } else {
         const int rj = j == 0 ? r[0] : j == 1 ? r[1] : j == 2 ? r[2] : r[3];
-        const unsigned int* src = (const unsigned int*)((KEY ? (const char*)p->tree : lb) + (unsigned)rj);
+        const unsigned int* src = (const unsigned int*)((const char*)p->tree + (unsigned)rj);
         ((unsigned int*)stage)[lane] = k0 + j < e ? src[w] : 0u;
       }
       __builtin_amdgcn_wave_barrier();
@@ -1866,16 +1747,13 @@ __device__ __forceinline__ int list_search_batch(KP p, const int32_t* ent, int b
       if (j > 0 && k0 + j >= e) break;
       if constexpr (KEY) {
         TriRegs T;
-        if constexpr (kStage) {
+        {
           const uint4 a = stage[4 * j + 0], bq = stage[4 * j + 1], c = stage[4 * j + 2], d4 = stage[4 * j + 3];
           T.v0[0] = __uint_as_float(a.x), T.v0[1] = __uint_as_float(a.y), T.v0[2] = __uint_as_float(a.z);
           T.id = a.w;
           T.e2[0] = __uint_as_float(bq.x), T.e2[1] = __uint_as_float(bq.y), T.e2[2] = __uint_as_float(bq.z);
           T.e1n[0] = __uint_as_float(c.x), T.e1n[1] = __uint_as_float(c.y), T.e1n[2] = __uint_as_float(c.z);
           T.nn[0] = __uint_as_float(d4.x), T.nn[1] = __uint_as_float(d4.y), T.nn[2] = __uint_as_float(d4.z);
-        } else {
-          (void)stage;
-          T = load_tri(rec<TriFast>(p, r[j]));
         }
         lanes();
 #pragma unroll
@@ -1883,7 +1761,7 @@ __device__ __forceinline__ int list_search_batch(KP p, const int32_t* ent, int b
           if ((fl >> k) & 1u) tri_test(T, ro[k], rd[k], key[k], tc[k]);
       } else {
         LRegs T;
-        if constexpr (kStage) {
+        {
           const uint4 a = stage[4 * j + 0], bq = stage[4 * j + 1], c = stage[4 * j + 2], d4 = stage[4 * j + 3];
           T.p[0] = __uint_as_float(a.x), T.p[1] = __uint_as_float(a.y), T.p[2] = __uint_as_float(a.z);
           T.cu = __uint_as_float(a.w);
@@ -1892,9 +1770,6 @@ __device__ __forceinline__ int list_search_batch(KP p, const int32_t* ent, int b
           T.tv[0] = __uint_as_float(c.x), T.tv[1] = __uint_as_float(c.y), T.tv[2] = __uint_as_float(c.z);
           T.ct = __uint_as_float(c.w);
           T.id = d4.x;
-        } else {
-          (void)stage;
-          T = load_ltri((const RT_CONST LTri*)(kCellRec ? rec_at(k0 + j) : lb + (unsigned)r[j]));
         }
         lanes();
 #pragma unroll
@@ -1976,9 +1851,6 @@ __device__ __forceinline__ bool gen_batch(KP p, const GroupPix& gp, int it0, con
       // an empty pixel list: no camera ray of the pixel can hit the mesh
       // (trace's no_mesh: the gate's verdict cannot matter)
       if ((pinfo & kPixCount) == 0u || ob.root < 0) continue;
-#ifdef RTMI_DIAG_GEN_NOCAM
-      continue;  // diagnostic build only (wrong images): the camera searches' share
-#endif
       F3 ro[S], rd[S];
       unsigned long long key[S], key0[S];
       float tc[S], unused[S];
@@ -2098,9 +1970,6 @@ __device__ __forceinline__ bool gen_batch(KP p, const GroupPix& gp, int it0, con
       const FObj ob = at(p->objs, i);
       if (i == mesh) {
         if ((li < 8 && ((skipw >> li) & 1u) != 0u) || ob.root < 0) continue;
-#ifdef RTMI_DIAG_GEN_NOSHADOW
-        continue;  // diagnostic build only (wrong images): the shadow searches' share
-#endif
         F3 ro[S], rd[S];
         unsigned long long pm[S], anyp = 0ull;
 #pragma unroll
@@ -2110,9 +1979,6 @@ __device__ __forceinline__ bool gen_batch(KP p, const GroupPix& gp, int it0, con
           anyp |= pm[k];
         }
         if (anyp == 0ull) continue;  // no lane enters the mesh's box
-#ifdef RTMI_DIAG_GEN_NOSHADOWSEARCH
-        continue;  // diagnostic build only (wrong images): the gated shadow searches' share
-#endif
         if (!p->grids || p->grids[li].gu <= 0) return false;  // the BVH: the caller's one-sample loop
         // mesh_search: the exact early exit's stop distance (the analytic
         // objects after the mesh), clamped below each lane's initial limit
@@ -2222,25 +2088,21 @@ __device__ __forceinline__ bool gen_batch(KP p, const GroupPix& gp, int it0, con
   return true;
 }
 
-// General pixels of the one-plane scenes (k_render_lean1's: one mesh + one
+// General pixels of the one-plane scenes (lean1q_loop's: one mesh + one
 // translated plane, distant lights, akGrid m | 64, every sample valid):
 // gen_batch with the two objects written out in scene order instead of the
 // object / dispatch loops — the plane's camera and shadow tests in
-// k_render_lean1's form, its normal (0, 1, 0), the albedo a select of the
+// lean1q_loop's form, its normal (0, 1, 0), the albedo a select of the
 // two objects' (no LDS stash), the camera's cx terms per lane and pixel.
 // The mesh searches (pixel list, light-grid cells, the early exit's stop)
 // are gen_batch's, unchanged. Returns false, before adding anything, where
 // gen_batch does (a shadow ray that needs the BVH). Frames and Stats
 // bit-identical to gen_batch (tests/test_gpu_split.py, RT_FLAG_NO_GEN1).
-// RTMI_GEN1_COMPACT=1 (A/B, row n2): the two samples' rays of a light cell
-// packed into one slot when they fit one wave (gen1_batch's cell loop).
-// Exact (frames and Stats bit-identical, GPU parity tests green) but slower:
-// C3 0.901 -> 0.918 ms, C5 78.5 -> 79.4 ms — the pairing and permutes cost
-// more than the face tests they save, and the kernel's spills grow from 4
-// to 18 VGPRs (DESIGN.md "Live-ray compaction of the light-cell searches").
-#ifndef RTMI_GEN1_COMPACT
-#define RTMI_GEN1_COMPACT 0
-#endif
+// (Packing the two samples' rays of a light cell into one slot when they fit
+// one wave was measured: exact but slower, C3 0.901 -> 0.918 ms, C5 78.5 ->
+// 79.4 ms — the pairing and permutes cost more than the face tests they save,
+// and the kernel's spills grow from 4 to 18 VGPRs; DESIGN.md "Live-ray
+// compaction of the light-cell searches".)
 template <int S, int NL>
 __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int it0, unsigned pinfo, Acc& acc,
                                            Stats32& wi) {
@@ -2292,9 +2154,6 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
   };
   auto camera_mesh = [&]() {
     if ((pinfo & kPixCount) == 0u || mob.root < 0) return;  // an empty pixel list: no camera ray can hit it
-#ifdef RTMI_DIAG_GEN_NOCAM
-    return;  // diagnostic build only (wrong images): the camera searches' share
-#endif
     F3 ro[S], rd[S];
     unsigned long long key[S], key0[S], anyp = 0ull, nomask[S];
     float tc[S], unused[S];
@@ -2383,7 +2242,7 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
       p = params();
       const FLight L = at(p->lights, li);
       const F3 sd = f3(-L.v[0], -L.v[1], -L.v[2]);
-      // the plane's shadow test (lean1's form: NaN multiplier when parallel)
+      // the plane's shadow test (lean1q_loop's form: NaN multiplier when parallel)
       const float mulp = fabsf(sd.y) > 1e-6f ? rcp(sd.y) : __builtin_nanf("");
       float ts[S], tpl[S];
 #pragma unroll
@@ -2402,9 +2261,6 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
       // the mesh (gen_batch's search), false: the BVH would be needed
       auto shadow_mesh = [&]() -> bool {
         if (((skipw >> li) & 1u) != 0u || mob.root < 0) return true;
-#ifdef RTMI_DIAG_GEN_NOSHADOW
-        return true;
-#endif
         F3 ro[S], rd[S];
         unsigned long long pm[S], anyp = 0ull;
 #pragma unroll
@@ -2412,15 +2268,9 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
           ro[k] = f3(so[k].x + mob.t[0], so[k].y + mob.t[1], so[k].z + mob.t[2]);
           rd[k] = sd;
           pm[k] = bal(lane_in(litm[k]) && mesh_gate(mob, slab_ray(ro[k], rd[k])));
-#ifdef RTMI_DIAG_GEN_NOMESHORIGIN
-          pm[k] &= ~bal(hm[k]);  // diagnostic build only (wrong images): mesh-origin shadow rays skip the mesh
-#endif
           anyp |= pm[k];
         }
         if (anyp == 0ull) return true;
-#ifdef RTMI_DIAG_GEN_NOSHADOWSEARCH
-        return true;  // diagnostic build only (wrong images): the gated shadow searches' share
-#endif
         const KP q = params();
         if (!q->grids || q->grids[li].gu <= 0) return false;
         // the exact early exit's stop: the plane after the mesh (if it is)
@@ -2432,10 +2282,6 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
           if (mesh == 0) stop[k] = tpl[k] >= 0.0f ? fminf(stop[k], tpl[k]) : stop[k];
         }
         const RT_CONST LightGrid& G = cp(q->grids)[li];
-#if RTMI_GEN1_COMPACT
-        __shared__ int cmp_lds_all[4][64];  // per wave: the lane pairing of a compacted cell search
-        int* cmp_lds = cmp_lds_all[threadIdx.x >> 6];
-#endif
         int cell[S];
         unsigned long long todo[S], left = 0ull, unsafe = 0ull;
 #pragma unroll
@@ -2476,68 +2322,6 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
             wi.v[STAT_LANE_NODES] += pc(own[k]);  // diagnostic: rays in searched cells
 #endif
           }
-#ifdef RTMI_DIAG_GEN_NOTESTS
-          continue;  // diagnostic build only (wrong images): the cell loop without its face tests
-#endif
-#if RTMI_GEN1_COMPACT
-          // Both samples have rays in this cell and together they fit one
-          // wave: sample 1's rays move into the lanes sample 0 leaves free
-          // (ballot + v_mbcnt ranks, the lane pairing through LDS, the ray
-          // state by ds_bpermute) and the cell's faces are tested once
-          // instead of twice; each ray's tests and its retirement are
-          // unchanged, so `best` (the only state the shade reads back: found /
-          // not found, and its order against `stop`) is the two-slot
-          // search's. Lanes outside the cell test faces as a harmless
-          // superset either way (list_search_batch).
-          if constexpr (S == 2) {
-            const unsigned long long m0 = own[0], m1 = own[1], fr0 = ~own[0];
-            const unsigned n1 = pc(m1);
-            if (fl == 3u && pc(m0) + n1 <= 64u) {
-              const int lane = (int)__lane_id();
-              const unsigned r1 = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u));
-              const unsigned rf = __builtin_amdgcn_mbcnt_hi((unsigned)(fr0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)fr0, 0u));
-              const bool src = lane_in(m1), dst = lane_in(fr0) && rf < n1;
-              int* pair = cmp_lds;
-              if (src) pair[r1] = lane;          // the r-th ray of sample 1 ...
-              __builtin_amdgcn_wave_barrier();
-              const int from = dst ? pair[rf] : lane;  // ... goes to the r-th free lane
-              __builtin_amdgcn_wave_barrier();
-              if (dst) pair[rf] = lane;
-              __builtin_amdgcn_wave_barrier();
-              const int to = src ? pair[r1] : lane;
-              __builtin_amdgcn_wave_barrier();
-              auto take = [&](float v0, float v1) {  // slot 0's value, or sample 1's from `from`
-                const float m = __int_as_float(__builtin_amdgcn_ds_bpermute(from << 2, __float_as_int(v1)));
-                return dst ? m : v0;
-              };
-              F3 ro_c[1] = {f3(take(ro[0].x, ro[1].x), take(ro[0].y, ro[1].y), take(ro[0].z, ro[1].z))};
-              const F3 rd_c[1] = {rd[0]};  // (both samples: the light's direction)
-              const float stop_c[1] = {take(stop[0], stop[1])};
-              float best_c[1] = {take(best[0], best[1])}, tc_c[1] = {take(tc[0], tc[1])};
-              const unsigned long long own_c[1] = {m0 | bal(dst)};
-              unsigned long long key_c[1] = {0ull};
-#ifdef RTMI_DIAG_LANES
-              unsigned dl = 0u;
-              const int nt = list_search_batch<1, false>(q, bent, cp(q->grid_off)[kb], cp(q->grid_off)[kb + 1], 1u, ro_c,
-                                                         rd_c, stop_c, own_c, key_c, best_c, tc_c, &dl, grid_rec_of(q, li, G));
-              wi.v[STAT_NODE_FETCH] += (unsigned)nt;
-              wi.v[STAT_LANE_NODES] += dl;
-#else
-              (void)list_search_batch<1, false>(q, bent, cp(q->grid_off)[kb], cp(q->grid_off)[kb + 1], 1u, ro_c, rd_c,
-                                                stop_c, own_c, key_c, best_c, tc_c, nullptr, grid_rec_of(q, li, G));
-#endif
-              // back: slot 0 in place, sample 1's rays from the lane they moved to
-              const float b1 = __int_as_float(__builtin_amdgcn_ds_bpermute(to << 2, __float_as_int(best_c[0])));
-              const float t1 = __int_as_float(__builtin_amdgcn_ds_bpermute(to << 2, __float_as_int(tc_c[0])));
-              const bool in0 = lane_in(m0);
-              best[0] = in0 ? best_c[0] : best[0];
-              tc[0] = in0 ? tc_c[0] : tc[0];
-              best[1] = src ? b1 : best[1];
-              tc[1] = src ? t1 : tc[1];
-              continue;
-            }
-          }
-#endif
 #ifdef RTMI_DIAG_LANES  // diagnostic: shadow face tests (x flagged samples) and the lanes still searching
           unsigned dl = 0u;
           const int nt = list_search_batch<S, false>(q, bent, cp(q->grid_off)[kb], cp(q->grid_off)[kb + 1], fl, ro, rd,
@@ -2880,14 +2664,10 @@ k_render_fast(const FastParams params_by_value) {
   int qj = 0;
   if (__lane_id() == 0) qj = (int)atomicAdd(head, 1u);
   qj = __builtin_amdgcn_readfirstlane(qj);
-  // reservations RTMI_QUEUE_AHEAD items ahead (lane 0 holds them): the
-  // atomic's round trip overlaps that many items
+  // the reservation one item ahead (lane 0 holds it): the atomic's round
+  // trip overlaps that item
   int qj_next = 0;
   if (__lane_id() == 0) qj_next = (int)atomicAdd(head, 1u);
-#if RTMI_QUEUE_AHEAD >= 2
-  int qj_next2 = 0;
-  if (__lane_id() == 0) qj_next2 = (int)atomicAdd(head, 1u);
-#endif
   int g = fast_item(qj, p->shards, shard);
   int nflush = 0;
   const int ngroups = list_items(p->list_n, p->ngroups, 1);
@@ -2948,9 +2728,7 @@ k_render_fast(const FastParams params_by_value) {
       // the remaining iterations one at a time — both compiled without any
       // mesh search
       int it = 0;
-#ifndef RTMI_NO_LEAN_BATCH
       for (; it + kLeanBatch <= iters; it += kLeanBatch) lean_batch<F>(p, gp, it, tb, pacc, ws);
-#endif
       if (it < iters) sample_loop(Bool<true>{}, it);
     } else if constexpr (!(F & (F_MESH | F_REFLECT | F_POINT)) && (F & (F_SPHERE | F_BOX)) != 0) {
       // analytic scenes with distant lights (C2): object-binned batches —
@@ -3003,12 +2781,7 @@ k_render_fast(const FastParams params_by_value) {
       nflush = 0;
     }
     qj = __builtin_amdgcn_readfirstlane(qj_next);
-#if RTMI_QUEUE_AHEAD >= 2
-    qj_next = qj_next2;
-    if (lane == 0) qj_next2 = (int)atomicAdd(head, 1u);
-#else
     if (lane == 0) qj_next = (int)atomicAdd(head, 1u);
-#endif
     g = fast_item(qj, p->shards, shard);
   }
   p = params();
@@ -3302,23 +3075,6 @@ k_render_lean(
   if (lane < kStatSlots) p->partials[(size_t)wave * kStatSlots + lane] = lds_tot[wib][lane];
 }
 
-// Lean pixels of a scene whose only analytic object is one plane (C3-C5: the
-// mesh on a ground plane), every transform a translation, NL distant lights
-// (1 or 2), akGrid with m | 64 and spp a multiple of 64 (every sample valid,
-// a lane's samples share one column) — rtmi.cpp lean1_ok decides. The same
-// per-sample arithmetic as lean_batch's uniform single-plane case, with what
-// that case leaves wave-uniform or per lane formed once:
-//  * the camera ray needs only its y direction (the plane test, the hit
-//    point's height); the cx terms of camera_ray_dir are per lane and pixel;
-//  * a plane's normal is (0, 1, 0), so every lit sample of the pixel has the
-//    same N, N.L per light and albedo: shadeDiffuse's term per light is one
-//    select of a uniform value, the colour lit ? albedo x E : background;
-//  * "t >= 0 and below the running limit" is, against a first (and only)
-//    object, one class test of t (finite, >= 0 incl. -0);
-//  * sample validity, object dispatch, the mesh skip and the per-object
-//    loops are gone (one plane, all samples valid).
-// Frames and Stats bit-identical to k_render_lean / k_render_fast
-// (tests/test_gpu_split.py, RT_FLAG_NO_LEAN1).
 // "t >= 0 and below the running limit" against a first object (limit
 // +inf): t in [-0, +inf), NaN excluded.
 // One v_cmp_class straight into a lane mask: classes -0, +0, +denormal,
@@ -3330,130 +3086,6 @@ __device__ __forceinline__ unsigned long long m_hit0(float t) {
   asm("v_cmp_class_f32_e64 %0, %1, %2" : "=s"(m) : "v"(t), "v"(0x1E0));
   return m;
 }
-template <int NL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_render_lean1(
-    const FastParams params_by_value) {
-  (void)params_by_value;
-  constexpr int S = 4;  // samples per lane per batch: the host requires iters % 4 == 0
-  const KP p = params();
-  __shared__ unsigned long long lds_tot[4][kStatSlots];
-  const int wib = (int)(threadIdx.x >> 6);
-  const int lane = (int)__lane_id();
-  if (lane < kStatSlots) lds_tot[wib][lane] = 0ull;
-  Stats32 ws;
-#pragma unroll
-  for (int k = 0; k < kStatSlots; ++k) ws.v[k] = 0u;
-  const int shard = (int)(blockIdx.x % (unsigned int)p->shards);
-  unsigned int* head = p->queue + shard * kQueueStride;
-  int qj = 0;
-  if (lane == 0) qj = (int)atomicAdd(head, 1u);
-  qj = __builtin_amdgcn_readfirstlane(qj);
-  int qj_next = 0;
-  if (lane == 0) qj_next = (int)atomicAdd(head, 1u);
-  int g = qj * p->shards + shard;
-  int nflush = 0;
-  const int iters = p->iters;
-  // the scene's one analytic object (the other is the mesh): a plane whose
-  // world -> object transform is a translation
-  const int po = p->shadow_mesh == 0 ? 1 : 0;
-  const FObj pl = at(p->objs, po);
-  const RT_CONST FObjX& plx = at(p->objx, po);
-  const float nroy = -(p->cam[1] + pl.t[1]);  // -(camera origin in plane space).y: Plane.intersect's -o.y
-  const float ty = pl.t[1], oy = p->cam[1], bias = p->bias;
-  // per light: the parallel shadow rays' plane reciprocal (a NaN multiplier
-  // when parallel: no t >= 0), N.L with N = (0, 1, 0) (dot3's roundings), ci
-  float mulp[NL], ndl[NL], ci[NL][3];
-#pragma unroll
-  for (int l = 0; l < NL; ++l) {
-    const FLight L = at(p->lights, l);
-    const F3 sd = f3(-L.v[0], -L.v[1], -L.v[2]);
-    mulp[l] = fabsf(sd.y) > 1e-6f ? rcp(sd.y) : __builtin_nanf("");
-    ndl[l] = fmaxf(dot3(f3(0.0f, 1.0f, 0.0f), sd), 0.0f);
-    ci[l][0] = L.ci[0];
-    ci[l][1] = L.ci[1];
-    ci[l][2] = L.ci[2];
-  }
-  const F3 alb = f3(plx.albedo_pi[0], plx.albedo_pi[1], plx.albedo_pi[2]);
-  const F3 bg = f3(p->bg[0], p->bg[1], p->bg[2]);
-  const int mm = p->grid_m - 1, lg = p->log2_grid_m;
-  const float st = p->sample_step, of = p->sample_off;
-  static_assert(kLeanRun == 4, "a run is one s_load_dwordx4");
-  using Run = int32_t __attribute__((ext_vector_type(4)));
-  const RT_CONST Run* runs = (const RT_CONST Run*)cp(p->order);
-  const int nruns = list_items(p->list_n, p->ngroups, kLeanRun);
-  Run ent = g < nruns ? runs[g] : Run{-1, -1, -1, -1};
-  while (g < nruns) {
-    qj = __builtin_amdgcn_readfirstlane(qj_next);
-    if (lane == 0) qj_next = (int)atomicAdd(head, 1u);
-    const int gn = qj * p->shards + shard;
-    const Run ent_next = gn < nruns ? runs[gn] : Run{-1, -1, -1, -1};
-#pragma unroll 1
-    for (int r = 0; r < kLeanRun; ++r) {
-      const int gg = ent.x;
-      ent = Run{ent.y, ent.z, ent.w, -1};
-      if (gg < 0) break;
-      GroupPix gp = group_pixel(p, gg, lane);
-      gp.valid = true;
-      // the lane's column: camera_ray_dir's cx terms, once per pixel
-      const float px = (float)gp.x + __builtin_fmaf((float)(gp.sub & mm), st, of);
-      const float cx = (px - p->cam_b) * p->cam_a;
-      const float q0 = __builtin_fmaf(cx, cx, 1.0f);
-      const float ay = __builtin_fmaf(cx, p->cam[4], -p->cam[10]);
-      const float pyb = (float)gp.y;
-      Acc acc;
-      acc.v = f3(0.0f, 0.0f, 0.0f);
-      unsigned nlit = 0u, nocc = 0u;
-#pragma unroll 1
-      for (int it0 = 0; it0 < iters; it0 += S) {
-        float soy[S];
-        unsigned long long litm[S];
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-          // castPrimaryRay's direction, y only; Plane.intersect; trace's rule
-          const int s = (it0 + k) * 64 + gp.sub;
-          const float py = pyb + __builtin_fmaf((float)(s >> lg), st, of);
-          const float cy = (p->cam_d - py) * p->cam_c;
-          const float rl = rsq(__builtin_fmaf(cy, cy, q0));
-          const float dy = __builtin_fmaf(cy, p->cam[7], ay) * rl;
-          const float t = fabsf(dy) > 1e-6f ? nroy * rcp(dy) : -finf();
-          litm[k] = m_hit0(t);  // the camera ray hits the plane: a hit, and a lit sample
-          nlit += pc(litm[k]);
-          // the shadow origin's height: hitW.y + N.y * bias (N.y = 1)
-          soy[k] = __builtin_fmaf(1.0f, bias, __builtin_fmaf(dy, t, oy));
-        }
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-          const bool lit = lane_in(litm[k]);
-          F3 E = f3(0.0f, 0.0f, 0.0f);
-#pragma unroll
-          for (int l = 0; l < NL; ++l) {
-            const float ts = -(soy[k] + ty) * mulp[l];
-            const unsigned long long occ = m_hit0(ts) & litm[k];  // the shadow ray hits the plane
-            nocc += pc(occ);
-            const float x = lane_in(litm[k] & ~occ) ? ndl[l] : 0.0f;
-            E = f3(__builtin_fmaf(ci[l][0], x, E.x), __builtin_fmaf(ci[l][1], x, E.y),
-                   __builtin_fmaf(ci[l][2], x, E.z));
-          }
-          const F3 a = mul3(alb, E);
-          acc_add3(acc, lit ? a.x : bg.x, lit ? a.y : bg.y, lit ? a.z : bg.z);
-        }
-      }
-      ws.v[STAT_PRIMARY] += (unsigned)(64 * iters);
-      ws.v[STAT_SHADOW] += (unsigned)NL * nlit;
-      ws.v[STAT_HITS] += nlit + nocc;  // camera hits (= lit samples) + shadow hits
-      finish_item(p, gp, acc.v, 64);
-    }
-    if (++nflush >= p->stat_flush) {
-      flush_stats(ws, lds_tot[wib], lane);
-      nflush = 0;
-    }
-    ent = ent_next;
-    g = gn;
-  }
-  flush_stats(ws, lds_tot[wib], lane);
-  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + threadIdx.x / 64u);
-  if (lane < kStatSlots) p->partials[(size_t)wave * kStatSlots + lane] = lds_tot[wib][lane];
-}
 
 // Work queue of one list of n items over `shards` heads at `queue`; the
 // blocks b with b % shards == s pull from head s, so shard s runs on XCD
@@ -3461,23 +3093,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 // Default: shard s hands out runs of R consecutive items, s R .. s R + R - 1,
 // then (s + S) R .., ... (every shard's items span the image; R = RUN: a run
 // of neighbouring pixels is written by one XCD, so fewer framebuffer lines
-// are written back partially by two XCDs' L2s). RTMI_XCD_CHUNK=1 (A/B only, measured slower: C3
-// 0.93 -> 1.10 ms, rank 0 of 8 0.165 -> 0.396 ms — the bunny's expensive
-// items fall into few chunks and the other XCDs end up stealing from one
-// head): the list is cut into S contiguous chunks,
-// chunk c = [c n / S, (c + 1) n / S), and the S / 8 shards of an XCD own
-// consecutive chunks (shard s: chunk (s % 8) S / 8 + s / 8; S a multiple of
-// 8, else chunk s) — the lists are in image tile order, so an XCD's waves
-// work on one horizontal slab of the image and its L2 holds that slab's faces
-// and cell lists. A wave whose chunk is exhausted moves on to the next chunk
-// (the next shard of its XCD, at the slab's end the next XCD's first) and
-// takes that chunk's next items, so no XCD idles while items remain; each
-// wave visits every chunk at most once (the loop ends). The next
-// reservation is fetched one item ahead (its atomic's latency hides behind
-// the item).
-#ifndef RTMI_XCD_CHUNK
-#define RTMI_XCD_CHUNK 0
-#endif
+// are written back partially by two XCDs' L2s). (One contiguous chunk of the
+// list per shard, an XCD's waves on one horizontal slab of the image, was
+// measured slower: C3 0.93 -> 1.10 ms, rank 0 of 8 0.165 -> 0.396 ms — the
+// bunny's expensive items fall into few chunks and the other XCDs end up
+// stealing from one head.) The next reservation is fetched one item ahead
+// (its atomic's latency hides behind the item).
 #ifndef RTMI_GEN_RUN
 #define RTMI_GEN_RUN 8   // general items (one pixel each): 8 pixels = 96 B of framebuffer per run
 #endif
@@ -3490,45 +3111,26 @@ struct WorkQ {
   int shards, n, cur, left, lo, len, qj_next, head;
 
   __device__ __forceinline__ void bounds() {
-#if RTMI_XCD_CHUNK
-    lo = (int)(((long long)cur * n) / shards);
-    len = (int)(((long long)(cur + 1) * n) / shards) - lo;
-    const int per = shards >> 3;  // chunks per XCD
-    head = (shards & 7) == 0 ? (cur % per) * 8 + cur / per : cur;
-#else
     head = cur;
     lo = cur;
     len = n;
-#endif
   }
   // (scalar at once: the compiler's atomic optimizer already waits for the
   // atomic and reads its result with readfirstlane where it is issued, so a
   // per-lane copy bought no latency hiding — it only held a VGPR across the
-  // item, which k_render_mix1 spilled)
-  // RTMI_QSCALAR=0 (A/B): the per-lane copy again (with the atomic
-  // optimiser off — Makefile F32_FLAGS — a true prefetch): C3 equal, one
-  // spilled VGPR in k_render_mix1 (profiles/r5/ab/r5af_*)
-#ifndef RTMI_QSCALAR
-#define RTMI_QSCALAR 1
-#endif
+  // item, which k_render_mix1 spilled; with the atomic optimiser off —
+  // Makefile F32_FLAGS — the per-lane copy is a true prefetch: C3 equal, one
+  // spilled VGPR in k_render_mix1, profiles/r5/ab/r5af_*)
   __device__ __forceinline__ int reserve() {
     int q = 0;
     if (__lane_id() == 0) q = (int)atomicAdd(queue + head * kQueueStride, 1u);
-    return RTMI_QSCALAR ? __builtin_amdgcn_readfirstlane(q) : q;
+    return __builtin_amdgcn_readfirstlane(q);
   }
   __device__ __forceinline__ int item(int qj) const {
-#if RTMI_XCD_CHUNK
-    return lo + qj;
-#else
     return (qj / RUN * shards + lo) * RUN + qj % RUN;
-#endif
   }
   __device__ __forceinline__ bool in(int qj) const {
-#if RTMI_XCD_CHUNK
-    return qj < len;
-#else
     return item(qj) < n;
-#endif
   }
   // the first item (-1: none)
   __device__ __forceinline__ int start(unsigned int* q, int s, int items) {
@@ -3536,11 +3138,7 @@ struct WorkQ {
     shards = s;
     n = items;
     const int shard = (int)(blockIdx.x % (unsigned int)s);
-#if RTMI_XCD_CHUNK
-    cur = (s & 7) == 0 ? (shard & 7) * (s >> 3) + (shard >> 3) : shard;
-#else
     cur = shard;
-#endif
     left = s;
     bounds();
     qj_next = reserve();
@@ -3554,14 +3152,7 @@ struct WorkQ {
         qj_next = reserve();
         return item(qj);
       }
-#if RTMI_XCD_CHUNK
-      if (--left <= 0) return -1;
-      cur = cur + 1 == shards ? 0 : cur + 1;
-      bounds();
-      qj_next = reserve();
-#else
       return -1;
-#endif
     }
   }
 };
@@ -3588,25 +3179,45 @@ __device__ __forceinline__ GroupPix lane_pixel(KP p, int g) {
   return r;
 }
 
-// The one-plane lean pixels with LP lanes per pixel (k_render_lean1's
-// arithmetic per sample, a different assignment of samples to lanes): lane
-// LP i + q of a wave renders "virtual lanes" V q .. V q + V - 1 (V = 64 / LP)
-// of pixel i of a (64 / LP)-pixel work item — the samples k_render_lean1's
-// lanes V q .. carry — each virtual lane's samples added in sample order as
-// there, a lane's V virtual lanes in the balanced pairwise order of
-// wave_total's DPP row scan (a binary-counter stack), then the lanes of the
-// pixel pairwise by xor shuffles (1, 2, 4, 8, ...): wave_total is that
-// balanced tree over the 64 lanes (row scans, then rows as ((R0 + R1) +
-// (R2 + R3))). So every pixel is the same float sum as in k_render_lean1,
-// bit for bit, with no per-pixel wave reduction and the per-pixel set-up
-// spread over 64 / LP pixels at once. LP = 4 (16 pixels per item) for whole
-// frames, 16 (4 per item) for short launches (rtmi.cpp).
+// Lean pixels of a scene whose only analytic object is one plane (C3-C5: the
+// mesh on a ground plane), every transform a translation, NL distant lights
+// (1 or 2), akGrid with m | 64 and spp a multiple of 256 (every sample valid,
+// a virtual lane's samples share one column) — rt_render.cpp lean1_ok
+// decides. The same per-sample arithmetic as lean_batch's uniform
+// single-plane case, with what that case leaves wave-uniform or per lane
+// formed once:
+//  * the camera ray needs only its y direction (the plane test, the hit
+//    point's height); the cx terms of camera_ray_dir are per virtual lane;
+//  * a plane's normal is (0, 1, 0), so every lit sample of the pixel has the
+//    same N, N.L per light and albedo: shadeDiffuse's term per light is one
+//    select of a uniform value, the colour lit ? albedo x E : background;
+//  * "t >= 0 and below the running limit" is, against a first (and only)
+//    object, one class test of t (m_hit0);
+//  * sample validity, object dispatch, the mesh skip and the per-object
+//    loops are gone (one plane, all samples valid).
+// Frames and Stats bit-identical to k_render_lean / k_render_fast
+// (tests/test_gpu_split.py, RT_FLAG_NO_LEAN1).
+// The pixel's float sum (ground1_batch and the uniform classes form the same
+// one): the pixel has 64 "virtual lanes", whatever LP is. Virtual lane v takes
+// the samples s = it * 64 + v, it = 0 .. iters - 1 — column v & (m - 1), row
+// s >> log2 m — each formed with the explicit FMAs written below (px, py from
+// exact small-integer floats, cx, cy and the ray's y as camera_ray_dir rounds
+// them, the shadow origin's height, E per light in light order, albedo x E),
+// and adds their colours to 0 in sample order, one float add per sample and
+// channel. The 64 partial sums are added as the balanced binary tree of
+// wave_total: v with v ^ 1, those sums with v ^ 2, then ^ 4, ... ^ 32; the
+// total times inv_len is the pixel.
+// With LP lanes per pixel, lane LP i + q of a wave renders virtual lanes
+// V q .. V q + V - 1 (V = 64 / LP) of pixel i of a (64 / LP)-pixel work item:
+// a lane's V virtual lanes are added in that tree's order by a binary-counter
+// stack, then the lanes of the pixel pairwise by xor shuffles (1, 2, 4, 8,
+// ...). So every pixel is that one float sum, bit for bit, with no per-pixel
+// wave reduction and the per-pixel set-up spread over 64 / LP pixels at once.
+// LP = 4 (16 pixels per item) for whole frames, 16 (4 per item) for short
+// launches (rt_render.cpp).
 // k_render_lean1q's work loop over one list (order: 64 / LP entries per
 // item, ngroups items, dequeued from the shard heads at `queue`); also the
 // second phase of k_render_mix1.
-#ifndef RTMI_LEAN1Q_H
-#define RTMI_LEAN1Q_H 1
-#endif
 template <int NL, int LP>
 __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngroups, unsigned int* queue, int shards,
                                             Stats32& ws, unsigned long long* tot, int& nflush) {
@@ -3640,7 +3251,7 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
   const float st = p->sample_step, of = p->sample_off;
   static_assert(LP == 4 || LP == 8 || LP == 16, "lanes per pixel");
   constexpr int V = 64 / LP;   // virtual lanes per lane
-  constexpr int H = RTMI_LEAN1Q_H;  // virtual lanes per step (independent sample chains)
+  constexpr int H = 1;  // virtual lanes per step (independent sample chains)
   static_assert(H == 1 || H == 2, "one or two virtual lanes per step");
   constexpr int PPI = 64 / LP; // pixels per work item
   const int q = lane & (LP - 1);  // this lane's share of its pixel's virtual lanes
@@ -3703,7 +3314,7 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
     // == it * (64 >> lg) + (jv >> lg) (m | 64), and jv >> lg == (q V) >> lg
     // for all of this lane's virtual lanes (m >= 16, rtmi.cpp lean1_ok, so V
     // divides 2^lg): one camera y per iteration for the whole lane, formed
-    // from exact small-integer floats as k_render_lean1 steps them
+    // from exact small-integer floats
     float rows = (float)(64 >> lg), sj0 = (float)((q * V) >> lg);
     // formed per item (opaque): hoisted out of the item loop, the four
     // per-lane row offsets below lived across every item and spilled
@@ -3723,7 +3334,7 @@ __device__ __forceinline__ void lean1q_loop(KP p, const int32_t* order, int ngro
       F3 acc[H];
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        const int jv = q * V + j + h;  // the virtual lane (k_render_lean1's lane)
+        const int jv = q * V + j + h;  // the virtual lane
         const float px = pxb + __builtin_fmaf((float)(jv & mm), st, of);
         const float cx = (px - p->cam_b) * p->cam_a;
         q0[h] = __builtin_fmaf(cx, cx, 1.0f);
@@ -3975,12 +3586,6 @@ __device__ __forceinline__ void gen1_loop(KP p, LdsF* ls, Stats32& ws, unsigned 
     const int ge = cp(p->order)[g];
     const bool gnd = (ge & kGenGroundBit) != 0 && p->ngroups <= kLeanIdxMask;
     const int gg = gnd ? ge & kLeanIdxMask : ge;
-#ifdef RTMI_DIAG_NOGROUND
-    if (gnd) {  // diagnostic build only (wrong images): what the ground pixels cost
-      g = wq.next();
-      continue;
-    }
-#endif
     GroupPix gp = group_pixel(p, gg, lane_id_fresh());
     gp.valid = true;  // the lists hold only pixels of the launch (rtmi.cpp split_lists)
     // a one-pixel group: its placement is wave-uniform (scalar registers;

@@ -219,8 +219,7 @@ __global__ __launch_bounds__(256) void k_frame_build1(const FrameLaunch a, int f
 // (C3, interleaved A/Bs, `profiles/r5/ab/r5aa_*`, `r5ab_*`): rank 0 of 8
 // (1,012 tiles) back to back 0.142 ms with 16 tiles per block, 0.137 with 4,
 // 0.136 with 2 or 1; the whole 1080p frame (8,100 tiles) 0.823 ms with 16,
-// 0.816 with 4. 4K frames (32,400 tiles) keep 16. RTMI_LISTS_CHUNK=1|2|4|16
-// forces one (diagnostic builds).
+// 0.816 with 4. 4K frames (32,400 tiles) keep 16.
 __host__ __forceinline__ int lists_chunk(int ntiles) { return ntiles <= 2048 ? 2 : ntiles <= 8192 ? 4 : 16; }
 
 // The class of a launch pixel: 1 lean (empty list, every light skipped), 2
@@ -486,19 +485,11 @@ extern "C" int rtmi_frame_build(const rtmi::FrameLaunch* a, void* stream) {
   hipLaunchKernelGGL(k_frame_build1, dim3(face_blocks + tile_blocks), dim3(256), 0, st, *a, face_blocks);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || a->ntiles <= 0) return (int)e;
-  static const int b2w = rtmi::diag_env("RTMI_B2_WAVES") ? std::atoi(rtmi::diag_env("RTMI_B2_WAVES")) : 4;  // diagnostic
-  if (b2w == 8)
-    hipLaunchKernelGGL(k_frame_build2<8>, dim3((unsigned)a->ntiles), dim3(256), 0, st, *a);
-  else
-    hipLaunchKernelGGL(k_frame_build2<4>, dim3((unsigned)a->ntiles), dim3(256), 0, st, *a);
+  hipLaunchKernelGGL(k_frame_build2<4>, dim3((unsigned)a->ntiles), dim3(256), 0, st, *a);
   if ((e = hipGetLastError()) != hipSuccess || !a->r.split) return (int)e;
-  static const int chunk_env = rtmi::diag_env("RTMI_LISTS_CHUNK") ? std::atoi(rtmi::diag_env("RTMI_LISTS_CHUNK")) : 0;
-  const int chunk = chunk_env == 1 || chunk_env == 2 || chunk_env == 4 || chunk_env == 16 ? chunk_env
-                                                                                          : lists_chunk(a->ntiles);
+  const int chunk = lists_chunk(a->ntiles);
   const int nchunks = (a->ntiles + chunk - 1) / chunk;
-  if (chunk == 1)
-    hipLaunchKernelGGL(k_frame_lists<1>, dim3((unsigned)nchunks), dim3(256), 0, st, *a);
-  else if (chunk == 2)
+  if (chunk == 2)
     hipLaunchKernelGGL(k_frame_lists<2>, dim3((unsigned)nchunks), dim3(256), 0, st, *a);
   else if (chunk == 4)
     hipLaunchKernelGGL(k_frame_lists<4>, dim3((unsigned)nchunks), dim3(256), 0, st, *a);

@@ -67,9 +67,7 @@ __global__ __launch_bounds__(256) void k_sec_add(float* __restrict__ fb, const l
 
 // the instrumented (RT_FLAG_COUNT_TRAVERSAL) kernel: all features
 template __global__ void fast::k_render_fast<true, fast::F_ALL>(const FastParams);
-// lean pixels of one-plane scenes (rtmi.cpp lean1_ok), one or two lights
-template __global__ void fast::k_render_lean1<1>(const FastParams);
-template __global__ void fast::k_render_lean1<2>(const FastParams);
+// lean pixels of one-plane scenes (rt_render.cpp lean1_ok), one or two lights, 4 or 16 lanes per pixel
 template __global__ void fast::k_render_lean1q<1, 4>(const FastParams);
 template __global__ void fast::k_render_lean1q<2, 4>(const FastParams);
 template __global__ void fast::k_render_lean1q<1, 16>(const FastParams);
@@ -85,65 +83,80 @@ template __global__ void fast::k_render_mix1<2, 16>(const FastParams);
 
 }  // namespace rtmi
 
-// feature-subset specialisations: rt_kernels_f32_part.hip, 16 objects
-#define RTMI_PART_DECL(k)                                                                             \
-  extern "C" int rtmi_launch_render_f32_part##k(unsigned, const rtmi::FastParams*, int, size_t, void*); \
-  extern "C" int rtmi_render_f32_part_blocks_per_cu##k(unsigned, size_t);                              \
-  extern "C" int rtmi_launch_lean_f32_part##k(unsigned, const rtmi::FastParams*, int, size_t, void*);   \
-  extern "C" int rtmi_lean_f32_part_blocks_per_cu##k(unsigned, size_t);                              \
-  extern "C" int rtmi_launch_gen_f32_part##k(unsigned, const rtmi::FastParams*, int, size_t, void*);    \
-  extern "C" int rtmi_gen_f32_part_blocks_per_cu##k(unsigned, size_t);                              \
-  extern "C" int rtmi_launch_wave_f32_part##k(unsigned, const rtmi::FastParams*, int, size_t, void*);   \
-  extern "C" int rtmi_wave_f32_part_blocks_per_cu##k(unsigned, size_t);
+// feature-subset specialisations: rt_kernels_f32_part.hip, 16 objects, each
+// exporting the address of kernel (family, subset) for its 8 subsets
+#define RTMI_PART_DECL(k) extern "C" const void* rtmi_f32_kernel_part##k(int, unsigned);
 RTMI_PART_DECL(0) RTMI_PART_DECL(1) RTMI_PART_DECL(2) RTMI_PART_DECL(3)
 RTMI_PART_DECL(4) RTMI_PART_DECL(5) RTMI_PART_DECL(6) RTMI_PART_DECL(7)
 RTMI_PART_DECL(8) RTMI_PART_DECL(9) RTMI_PART_DECL(10) RTMI_PART_DECL(11)
 RTMI_PART_DECL(12) RTMI_PART_DECL(13) RTMI_PART_DECL(14) RTMI_PART_DECL(15)
+#undef RTMI_PART_DECL
 
 namespace {
-#define RTMI_L(k) rtmi_launch_render_f32_part##k
-#define RTMI_O(k) rtmi_render_f32_part_blocks_per_cu##k
-int (*const kLaunch[16])(unsigned, const rtmi::FastParams*, int, size_t, void*) = {
-    RTMI_L(0), RTMI_L(1), RTMI_L(2),  RTMI_L(3),  RTMI_L(4),  RTMI_L(5),  RTMI_L(6),  RTMI_L(7),
-    RTMI_L(8), RTMI_L(9), RTMI_L(10), RTMI_L(11), RTMI_L(12), RTMI_L(13), RTMI_L(14), RTMI_L(15)};
-int (*const kOccupancy[16])(unsigned, size_t) = {
-    RTMI_O(0), RTMI_O(1), RTMI_O(2),  RTMI_O(3),  RTMI_O(4),  RTMI_O(5),  RTMI_O(6),  RTMI_O(7),
-    RTMI_O(8), RTMI_O(9), RTMI_O(10), RTMI_O(11), RTMI_O(12), RTMI_O(13), RTMI_O(14), RTMI_O(15)};
-#define RTMI_LL(k) rtmi_launch_lean_f32_part##k
-#define RTMI_LO(k) rtmi_lean_f32_part_blocks_per_cu##k
-int (*const kLaunchLean[16])(unsigned, const rtmi::FastParams*, int, size_t, void*) = {
-    RTMI_LL(0), RTMI_LL(1), RTMI_LL(2),  RTMI_LL(3),  RTMI_LL(4),  RTMI_LL(5),  RTMI_LL(6),  RTMI_LL(7),
-    RTMI_LL(8), RTMI_LL(9), RTMI_LL(10), RTMI_LL(11), RTMI_LL(12), RTMI_LL(13), RTMI_LL(14), RTMI_LL(15)};
-int (*const kOccupancyLean[16])(unsigned, size_t) = {
-    RTMI_LO(0), RTMI_LO(1), RTMI_LO(2),  RTMI_LO(3),  RTMI_LO(4),  RTMI_LO(5),  RTMI_LO(6),  RTMI_LO(7),
-    RTMI_LO(8), RTMI_LO(9), RTMI_LO(10), RTMI_LO(11), RTMI_LO(12), RTMI_LO(13), RTMI_LO(14), RTMI_LO(15)};
-#define RTMI_LG(k) rtmi_launch_gen_f32_part##k
-#define RTMI_GO(k) rtmi_gen_f32_part_blocks_per_cu##k
-int (*const kLaunchGen[16])(unsigned, const rtmi::FastParams*, int, size_t, void*) = {
-    RTMI_LG(0), RTMI_LG(1), RTMI_LG(2),  RTMI_LG(3),  RTMI_LG(4),  RTMI_LG(5),  RTMI_LG(6),  RTMI_LG(7),
-    RTMI_LG(8), RTMI_LG(9), RTMI_LG(10), RTMI_LG(11), RTMI_LG(12), RTMI_LG(13), RTMI_LG(14), RTMI_LG(15)};
-int (*const kOccupancyGen[16])(unsigned, size_t) = {
-    RTMI_GO(0), RTMI_GO(1), RTMI_GO(2),  RTMI_GO(3),  RTMI_GO(4),  RTMI_GO(5),  RTMI_GO(6),  RTMI_GO(7),
-    RTMI_GO(8), RTMI_GO(9), RTMI_GO(10), RTMI_GO(11), RTMI_GO(12), RTMI_GO(13), RTMI_GO(14), RTMI_GO(15)};
-#define RTMI_LW(k) rtmi_launch_wave_f32_part##k
-#define RTMI_WO(k) rtmi_wave_f32_part_blocks_per_cu##k
-int (*const kLaunchWave[16])(unsigned, const rtmi::FastParams*, int, size_t, void*) = {
-    RTMI_LW(0), RTMI_LW(1), RTMI_LW(2),  RTMI_LW(3),  RTMI_LW(4),  RTMI_LW(5),  RTMI_LW(6),  RTMI_LW(7),
-    RTMI_LW(8), RTMI_LW(9), RTMI_LW(10), RTMI_LW(11), RTMI_LW(12), RTMI_LW(13), RTMI_LW(14), RTMI_LW(15)};
-int (*const kOccupancyWave[16])(unsigned, size_t) = {
-    RTMI_WO(0), RTMI_WO(1), RTMI_WO(2),  RTMI_WO(3),  RTMI_WO(4),  RTMI_WO(5),  RTMI_WO(6),  RTMI_WO(7),
-    RTMI_WO(8), RTMI_WO(9), RTMI_WO(10), RTMI_WO(11), RTMI_WO(12), RTMI_WO(13), RTMI_WO(14), RTMI_WO(15)};
+
+// Kernel (family: rt_common.h K32_*) of a feature subset; null: the family
+// has none for the subset.
+const void* subset_kernel(int family, unsigned subset) {
+#define RTMI_K(k) rtmi_f32_kernel_part##k
+  static const void* (*const kPart[16])(int, unsigned) = {
+      RTMI_K(0), RTMI_K(1), RTMI_K(2),  RTMI_K(3),  RTMI_K(4),  RTMI_K(5),  RTMI_K(6),  RTMI_K(7),
+      RTMI_K(8), RTMI_K(9), RTMI_K(10), RTMI_K(11), RTMI_K(12), RTMI_K(13), RTMI_K(14), RTMI_K(15)};
+#undef RTMI_K
+  return kPart[(subset >> 3) & 15u](family, subset & 127u);
+}
+
+// The one-plane kernels (rt_render.cpp lean1_ok) for nl (1 or 2) distant
+// lights: lean (k_render_lean1q) and merged (k_render_mix1) with lp (4 or 16)
+// lanes per lean pixel, and the batched general one; null: no such kernel.
+const void* lean1_kernel(bool mix, int nl, int lp) {
+  using namespace rtmi::fast;
+  static const void* const k[2][2][2] = {
+      {{(const void*)k_render_lean1q<1, 4>, (const void*)k_render_lean1q<1, 16>},
+       {(const void*)k_render_lean1q<2, 4>, (const void*)k_render_lean1q<2, 16>}},
+      {{(const void*)k_render_mix1<1, 4>, (const void*)k_render_mix1<1, 16>},
+       {(const void*)k_render_mix1<2, 4>, (const void*)k_render_mix1<2, 16>}}};
+  if ((nl != 1 && nl != 2) || (lp != 4 && lp != 16)) return nullptr;
+  return k[mix ? 1 : 0][nl - 1][lp == 16 ? 1 : 0];
+}
+
+const void* gen1_kernel(int nl) {
+  return nl == 1   ? (const void*)rtmi::fast::k_render_gen1<1>
+         : nl == 2 ? (const void*)rtmi::fast::k_render_gen1<2>
+                   : nullptr;
+}
+
+// Every float32 render kernel takes the FastParams by value, 256 threads per
+// block. fn null: `missing`.
+int launch_f32(const void* fn, hipError_t missing, const rtmi::FastParams* p, int blocks, size_t shmem, void* stream) {
+  if (!fn) return (int)missing;
+  void* args[] = {const_cast<rtmi::FastParams*>(p)};
+  (void)hipLaunchKernel(fn, dim3(blocks), dim3(256), args, shmem, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
+// Resident 256-thread blocks per CU of a kernel (grid sizing for the
+// work-queue loops: launch exactly what fits, waves pull items); 1 when the
+// runtime cannot say. fn null: `missing`.
+int blocks_per_cu(const void* fn, int missing, size_t shmem) {
+  if (!fn) return missing;
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, shmem);
+  return e == hipSuccess && nb > 0 ? nb : 1;
+}
+
+const void* count_kernel() { return (const void*)rtmi::fast::k_render_fast<true, rtmi::fast::F_ALL>; }
+
 }  // namespace
 
 // The reflection-compacting kernel of a reflective feature subset.
 extern "C" int rtmi_launch_wave_f32(const rtmi::FastParams* p, unsigned subset, int blocks, size_t shmem,
                                     void* stream) {
-  return kLaunchWave[(subset >> 3) & 15u](subset & 127u, p, blocks, shmem, stream);
+  return launch_f32(subset_kernel(rtmi::K32_WAVE, subset), hipErrorInvalidDeviceFunction, p, blocks, shmem, stream);
 }
 
 // Resident blocks per CU of the reflection-compacting kernel; 0: none for the subset.
 extern "C" int rtmi_wave_f32_blocks_per_cu(unsigned subset, size_t shmem) {
-  return kOccupancyWave[(subset >> 3) & 15u](subset & 127u, shmem);
+  return blocks_per_cu(subset_kernel(rtmi::K32_WAVE, subset), 0, shmem);
 }
 
 // fb[i] += sec[i] (32.32 fixed point) * scale where sec[i] != 0, i < n
@@ -157,138 +170,59 @@ extern "C" int rtmi_launch_sec_add(float* fb, const long long* sec, size_t n, fl
 // The batched general-pixel kernel of a feature subset (two-class launches).
 extern "C" int rtmi_launch_gen_f32(const rtmi::FastParams* p, unsigned subset, int blocks, size_t shmem,
                                    void* stream) {
-  return kLaunchGen[(subset >> 3) & 15u](subset & 127u, p, blocks, shmem, stream);
+  return launch_f32(subset_kernel(rtmi::K32_GEN, subset), hipErrorInvalidDeviceFunction, p, blocks, shmem, stream);
 }
 
 // Resident blocks per CU of the batched general kernel; 0: none for the subset.
 extern "C" int rtmi_gen_f32_blocks_per_cu(unsigned subset, size_t shmem) {
-  return kOccupancyGen[(subset >> 3) & 15u](subset & 127u, shmem);
+  return blocks_per_cu(subset_kernel(rtmi::K32_GEN, subset), 0, shmem);
 }
 
 // The lean-pixel kernel of a feature subset (two-class launches).
 extern "C" int rtmi_launch_lean_f32(const rtmi::FastParams* p, unsigned subset, int blocks, size_t shmem,
                                     void* stream) {
-  return kLaunchLean[(subset >> 3) & 15u](subset & 127u, p, blocks, shmem, stream);
+  return launch_f32(subset_kernel(rtmi::K32_LEAN, subset), hipErrorInvalidDeviceFunction, p, blocks, shmem, stream);
 }
 
 // Resident blocks per CU of the lean-pixel kernel; 0: no lean kernel for the subset.
 extern "C" int rtmi_lean_f32_blocks_per_cu(unsigned subset, size_t shmem) {
-  return kOccupancyLean[(subset >> 3) & 15u](subset & 127u, shmem);
+  return blocks_per_cu(subset_kernel(rtmi::K32_LEAN, subset), 0, shmem);
 }
 
-// k_render_lean1q (lp = 4 or 16 lanes per pixel, 64 / lp pixels per work
-// item) instead of k_render_lean1 (lp = 64: one pixel per wave, a run of 4
-// per item); RTMI_LEAN1Q=0 picks the latter (diagnostic A/B).
-extern "C" int rtmi_lean1_quads() {
-  static const int q = [] {
-    const char* e = rtmi::diag_env("RTMI_LEAN1Q");
-    return e ? std::atoi(e) : 1;
-  }();
-  return q;
-}
-
-// The one-plane lean-pixel kernel for nl (1 or 2) distant lights, lp lanes per pixel.
+// The one-plane lean-pixel kernel for nl (1 or 2) distant lights, lp (4 or
+// 16) lanes per pixel: 64 / lp pixels per work item.
 extern "C" int rtmi_launch_lean1_f32(const rtmi::FastParams* p, int nl, int lp, int blocks, void* stream) {
-  if (lp == 4 || lp == 16) {
-    using namespace rtmi::fast;
-#define RTMI_LQ(nl_, lp_) \
-  if (nl == nl_ && lp == lp_) { \
-    hipLaunchKernelGGL((k_render_lean1q<nl_, lp_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p); \
-    return (int)hipGetLastError(); \
-  }
-    RTMI_LQ(1, 4) RTMI_LQ(2, 4) RTMI_LQ(1, 16) RTMI_LQ(2, 16)
-#undef RTMI_LQ
-    return (int)hipErrorInvalidValue;
-  }
-  if (nl == 1)
-    hipLaunchKernelGGL(rtmi::fast::k_render_lean1<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p);
-  else if (nl == 2)
-    hipLaunchKernelGGL(rtmi::fast::k_render_lean1<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p);
-  else
-    return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_f32(lean1_kernel(false, nl, lp), hipErrorInvalidValue, p, blocks, 0, stream);
 }
 
-// Resident blocks per CU of the one-plane lean kernel actually launched:
-// k_render_lean1q<nl, lp> (lp = 4 or 16), k_render_lean1<nl> (lp = 64).
-extern "C" int rtmi_lean1_f32_blocks_per_cu(int nl, int lp) {
-  using namespace rtmi::fast;
-  int nb = 0;
-  hipError_t e = hipErrorInvalidValue;
-#define RTMI_OQ(nl_, lp_) \
-  if (nl == nl_ && lp == lp_) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_render_lean1q<nl_, lp_>, 256, 0);
-  RTMI_OQ(1, 4) RTMI_OQ(2, 4) RTMI_OQ(1, 16) RTMI_OQ(2, 16)
-#undef RTMI_OQ
-  if (lp == 64 && (nl == 1 || nl == 2))
-    e = nl == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_render_lean1<1>, 256, 0)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_render_lean1<2>, 256, 0);
-  return e == hipSuccess && nb > 0 ? nb : 1;
-}
+// Resident blocks per CU of k_render_lean1q<nl, lp>.
+extern "C" int rtmi_lean1_f32_blocks_per_cu(int nl, int lp) { return blocks_per_cu(lean1_kernel(false, nl, lp), 1, 0); }
 
 // The one-plane batched general-pixel kernel for nl (1 or 2) distant lights.
 extern "C" int rtmi_launch_gen1_f32(const rtmi::FastParams* p, int nl, int blocks, void* stream) {
-  if (nl == 1)
-    hipLaunchKernelGGL(rtmi::fast::k_render_gen1<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p);
-  else if (nl == 2)
-    hipLaunchKernelGGL(rtmi::fast::k_render_gen1<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p);
-  else
-    return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_f32(gen1_kernel(nl), hipErrorInvalidValue, p, blocks, 0, stream);
 }
+
+extern "C" int rtmi_gen1_f32_blocks_per_cu(int nl) { return blocks_per_cu(gen1_kernel(nl == 1 ? 1 : 2), 1, 0); }
 
 // The one-plane merged kernel (general items, then lean items with lp lanes per pixel).
 extern "C" int rtmi_launch_mix1_f32(const rtmi::FastParams* p, int nl, int lp, int blocks, void* stream) {
-  using namespace rtmi::fast;
-#define RTMI_MX(nl_, lp_) \
-  if (nl == nl_ && lp == lp_) { \
-    hipLaunchKernelGGL((k_render_mix1<nl_, lp_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p); \
-    return (int)hipGetLastError(); \
-  }
-  RTMI_MX(1, 4) RTMI_MX(2, 4) RTMI_MX(1, 16) RTMI_MX(2, 16)
-#undef RTMI_MX
-  return (int)hipErrorInvalidValue;
+  return launch_f32(lean1_kernel(true, nl, lp), hipErrorInvalidValue, p, blocks, 0, stream);
 }
 
-// Resident blocks per CU of k_render_mix1<nl, lp> (ADVICE r2: each launched
+// Resident blocks per CU of k_render_mix1<nl, lp> (each launched
 // instantiation sized from its own register use).
-extern "C" int rtmi_mix1_f32_blocks_per_cu(int nl, int lp) {
-  using namespace rtmi::fast;
-  int nb = 0;
-  hipError_t e = hipErrorInvalidValue;
-#define RTMI_OM(nl_, lp_) \
-  if (nl == nl_ && lp == lp_) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_render_mix1<nl_, lp_>, 256, 0);
-  RTMI_OM(1, 4) RTMI_OM(2, 4) RTMI_OM(1, 16) RTMI_OM(2, 16)
-#undef RTMI_OM
-  return e == hipSuccess && nb > 0 ? nb : 1;
-}
+extern "C" int rtmi_mix1_f32_blocks_per_cu(int nl, int lp) { return blocks_per_cu(lean1_kernel(true, nl, lp), 1, 0); }
 
-extern "C" int rtmi_gen1_f32_blocks_per_cu(int nl) {
-  int nb = 0;
-  const hipError_t e = nl == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtmi::fast::k_render_gen1<1>, 256, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtmi::fast::k_render_gen1<2>, 256, 0);
-  return e == hipSuccess && nb > 0 ? nb : 1;
-}
-
+// The render kernel of a feature subset, or the instrumented one (all features).
 extern "C" int rtmi_launch_render_f32(const rtmi::FastParams* p, unsigned subset, int blocks, size_t shmem,
                                       void* stream) {
-  if (p->flags & rtmi::RT_DEV_FLAG_COUNT) {
-    hipLaunchKernelGGL((rtmi::fast::k_render_fast<true, rtmi::fast::F_ALL>), dim3(blocks), dim3(256), shmem,
-                       (hipStream_t)stream, *p);
-    return (int)hipGetLastError();
-  }
-  return kLaunch[(subset >> 3) & 15u](subset & 127u, p, blocks, shmem, stream);
+  const void* fn = (p->flags & rtmi::RT_DEV_FLAG_COUNT) ? count_kernel() : subset_kernel(rtmi::K32_FAST, subset);
+  return launch_f32(fn, hipErrorInvalidDeviceFunction, p, blocks, shmem, stream);
 }
 
-// Resident 256-thread blocks per CU of the render kernel (grid sizing for the
-// work-queue loop: launch exactly what fits, waves pull pixel groups).
 extern "C" int rtmi_render_f32_blocks_per_cu(int count, unsigned subset, size_t shmem) {
-  if (count) {
-    int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nb, rtmi::fast::k_render_fast<true, rtmi::fast::F_ALL>, 256, shmem);
-    return e == hipSuccess && nb > 0 ? nb : 1;
-  }
-  return kOccupancy[(subset >> 3) & 15u](subset & 127u, shmem);
+  return blocks_per_cu(count ? count_kernel() : subset_kernel(rtmi::K32_FAST, subset), 1, shmem);
 }
 
 extern "C" int rtmi_launch_reduce_stats(const unsigned long long* partials, int num_waves,

@@ -111,12 +111,9 @@ int check_options(const rt_scene* s, const rt_options* o) {
 // 8). The count does not depend on the binning / batching flags, so
 // RT_FLAG_NO_BINNING and RT_FLAG_NO_OBJ_BATCH frames stay bit-identical (the
 // same samples per lane, summed in the same order).
-int f32_lanes(const rt_scene* s, const rt_options* o, int spp) {
-  // diagnostic A/B: RTMI_MAX_LANES caps the lanes per pixel
-  static const int max_lanes = rtmi::diag_env("RTMI_MAX_LANES") ? std::atoi(rtmi::diag_env("RTMI_MAX_LANES")) : 64;
+int f32_lanes(unsigned sub, int spp) {
   int L = 1;
-  while (L * 2 <= std::min(std::min(spp, 64), std::max(1, max_lanes))) L *= 2;
-  const unsigned sub = f32_subset(s, o);
+  while (L * 2 <= std::min(spp, 64)) L *= 2;
   const bool ob_batch = !(sub & (SUB_MESH | SUB_REFLECT | SUB_POINT)) && (sub & (SUB_SPHERE | SUB_BOX));
   const int lmin = kObjBatch > 4 ? 8 : 16;  // <= 8 pixels per wave (the kernel's object-mask union)
   while (ob_batch && L > lmin && spp / L < kObjBatch) L /= 2;
@@ -125,27 +122,82 @@ int f32_lanes(const rt_scene* s, const rt_options* o, int spp) {
 
 // Dynamic LDS of a float32 launch: the (multi-)jittered tables, 64/L
 // pixels per wave x 2 x spp floats x 4 waves per block.
-size_t f32_table_lds(const rt_scene* s, const rt_options* o) {
-  if (o->precision != RT_FP32 || o->aa_kind < RT_AA_MULTI_JITTERED) return 0;
+size_t f32_table_lds(const rt_options* o, int L) {
+  if (o->aa_kind < RT_AA_MULTI_JITTERED) return 0;
   const int spp = o->grid_size * o->grid_size;
-  const int L = f32_lanes(s, o, spp);
   return (size_t)4 * (64 / L) * 2 * (size_t)spp * sizeof(float);
 }
 
-// Lanes per pixel (L), pixels per wave tile, number of wave groups, grid.
+// What a float32 call launches, decided once before its per-call build
+// (plan_mapping, then plan_kernels): fill_fast hands the build the classes
+// the chosen kernels understand, launch() launches the chosen kernels. The
+// one thing known only after the build is whether the camera has pixel lists;
+// without them a two-class plan falls back to the one-kernel launch.
+// *_bpc: resident blocks per CU of a kernel the plan chose, asked of the
+// runtime at most once per call (0: not asked, or no such kernel).
 struct Plan {
-  int L, log2L, tx, ty, tiles_x, ngroups, blocks;
+  // the kernel specialisation (f32_subset) and its dynamic LDS
+  unsigned sub;
+  size_t shmem;
+  // lanes per pixel (L), pixels per wave tile, number of wave groups; the
+  // grid of the one-kernel launch, from fast_bpc
+  int L, log2L, tx, ty, tiles_x, ngroups, blocks, fast_bpc;
+  // the call builds camera-dependent data: binning on, a wave spans at most
+  // 4 pixels, every sample inside its pixel
+  bool build;
+  // one-pixel groups (L == 64): the build writes pixel records
+  bool records;
+  // the call may run as a two-class launch: not for instrumented launches,
+  // a measuring launch of a launch order or a cost dump, at most 8 lights
+  bool want_split;
+  // ... and does, when the build finds lists: want_split with records, no
+  // launch order, and a lean kernel for the subset (lean_bpc > 0). Every
+  // field below but `wave` is false / 0 without it.
+  bool two_class;
+  int lean_bpc;
+  // lean1_ok: implies one mesh object (shadow_mesh >= 0) and no point light
+  bool one_plane;
+  // the general list goes to the batched kernel: RT_FLAG_NO_BATCH off, one
+  // mesh object, light grids, no point light, a kernel for the subset
+  // (gen_bpc > 0). (launch() also asked for pixel lists: a two-class launch
+  // always has them.)
+  bool gen;
+  int gen_bpc;
+  // ... to gen1_loop: gen && one_plane && !RT_FLAG_NO_GEN1
+  bool gen1;
+  // the lean list goes to lean1q_loop: one_plane && !RT_FLAG_NO_LEAN1
+  bool lean1;
+  // lanes per lean pixel: 4 or 16 with lean1 (64 / lp pixels per item), else
+  // 64 (k_render_lean, runs of kLeanRun pixels)
+  int lp;
+  // both lists in one kernel (k_render_mix1): gen1 && lean1 && !RT_FLAG_NO_MIX
+  bool mix;
+  // the build tags lean entries with their uniform class, which only
+  // lean1q_loop reads: lean1 && !RT_FLAG_NO_UNIFORM && the group index fits
+  // below the class (ncols * nrows <= kLeanIdxMask)
+  bool uniform;
+  // the build tags general entries with the ground bit, which only gen1_loop
+  // reads: gen1 && !RT_FLAG_NO_GROUND1 && ncols * nrows <= kLeanIdxMask
+  bool ground;
+  // the kernels a two-stream launch is sized from (mix: mix_bpc alone):
+  // k_render_gen1 (gen1; else gen_bpc, or the mapping's grid), and the lean
+  // list's kernel — k_render_lean1q<nl, lp> or k_render_lean
+  int gen1_bpc, lean_list_bpc, mix_bpc;
+  // one-kernel launches of reflective scenes: reflected rays compacted per
+  // wave (k_render_wave, wave_bpc > 0). Never with two_class: the lean kernel
+  // exists only for subsets without reflection.
+  bool wave;
+  int wave_bpc;
 };
 
 Plan plan_mapping(const rt_scene* s, const rt_options* o, const Mapping& mp, int spp) {
   Plan pl{};
-  // float64 parity mode keeps the reference's sequential sample sum (one
-  // lane per pixel); float32 spreads a pixel's samples over up to 64 lanes.
-  int L = 1, lg = 0;
-  if (o->precision == RT_FP32) {
-    L = f32_lanes(s, o, spp);
-    while ((1 << lg) < L) ++lg;
-  }
+  pl.sub = f32_subset(s, o);
+  // a pixel's samples spread over up to 64 lanes
+  const int L = f32_lanes(pl.sub, spp);
+  int lg = 0;
+  while ((1 << lg) < L) ++lg;
+  pl.shmem = f32_table_lds(o, L);
   const int P = 64 / L;
   int tx = 1, ty = 1;
   switch (P) {
@@ -166,12 +218,9 @@ Plan plan_mapping(const rt_scene* s, const rt_options* o, const Mapping& mp, int
   const long long ng = (long long)pl.tiles_x * tiles_y;
   pl.ngroups = (int)std::min<long long>(ng, INT32_MAX);
   const long long want = (ng + 3) / 4;
-  long long cap = s->max_waves / 4;
-  if (o->precision == RT_FP32) {  // work-queue kernel: launch what is resident
-    const int per_cu = rtmi_render_f32_blocks_per_cu((o->flags & RT_FLAG_COUNT_TRAVERSAL) ? 1 : 0,
-                                                     f32_subset(s, o), f32_table_lds(s, o));
-    cap = std::min<long long>(cap, (long long)per_cu * s->num_cus);
-  }
+  // work-queue kernel: launch what is resident
+  pl.fast_bpc = rtmi_render_f32_blocks_per_cu((o->flags & RT_FLAG_COUNT_TRAVERSAL) ? 1 : 0, pl.sub, pl.shmem);
+  const long long cap = std::min<long long>(s->max_waves / 4, (long long)pl.fast_bpc * s->num_cus);
   pl.blocks = (int)std::max(1LL, std::min<long long>(want, cap));
   return pl;
 }
@@ -315,14 +364,14 @@ FrameRows frame_rows(const Mapping& mp, int height) {
 int frame_buffers(rt_scene* s, int w, int h, hipStream_t st) {
   rt_scene::Frame& f = s->fr;
   const bool lists = s->binnable && !s->bin_tris.empty();
-  // slots per pixel: 2^want_lg when set (test hook / RTMI_SLOT_LG), else
+  // slots per pixel: 2^want_lg when set (the test hook), else
   // as many as 2^27 entries (512 MB) allow, 32 to 256: a mesh's per-pixel
   // lists are longer the fewer pixels it covers (the bunny: 28 faces at most
   // at 1080p, past 32 for 7 % of its pixels at 320x180); a pixel past its
   // slots takes the BVH (exact, slower)
   int lg = f.want_lg >= 0 ? f.want_lg : slot_lg_for(w, h);
   // slot indices are 32-bit (pixel << lg + slot, int in the kernels): a
-  // requested lg (test hook / diagnostic) is clamped to keep the block below
+  // requested lg (test hook) is clamped to keep the block below
   // 2^31 entries
   while (lg > 0 && (((unsigned long long)w * (unsigned long long)h) << lg) + kBinPad >= (1ull << 31)) --lg;
   if (f.w == w && f.h == h && (!lists || f.slot_lg == lg)) return RT_OK;
@@ -447,8 +496,6 @@ int frame_build(rt_scene* s, const rt_options* o, const Mapping& mp, const FastP
   records_launch(s, o, mp, p, records, split, uniform, ground, a.r);
   a.tile_bits = f.tiles.p;
   a.tile_cls = f.status.p;
-  static const int diag_b2 = rtmi::diag_env("RTMI_DIAG_B2") ? std::atoi(rtmi::diag_env("RTMI_DIAG_B2")) : 0;
-  a.diag = diag_b2;  // diagnostic builds only (probe modes, wrong images)
   a.tiles_x = (mp.ncols + 63) / 64;
   a.ntiles = a.tiles_x * ((mp.nrows + 3) / 4);
   a.zero = zero;
@@ -511,17 +558,96 @@ bool sampler_in_pixel(int32_t aa_kind) {
   }
 }
 
-bool lean1_ok(const rt_scene* s, const rt_options* o, const FastParams& p, unsigned sub);
+// diagnostic builds (tools/cost_map.py): RTMI_COST_DUMP=<file> records every
+// pixel group's duration (s_memtime cycles) of a launch into <file>
+const char* cost_dump_path() {
+  static const char* path = rtmi::diag_env("RTMI_COST_DUMP");
+  return path;
+}
 
-// The float32 launch's parameters, and this call's camera-dependent data
-// built on the device (rt_frame.h) in stream order before the render
+// The lean pixels of a two-class launch go to lean1q_loop (rt_fast.h) when
+// the scene's only analytic object is one plane and every transform a
+// translation (the mesh + plane feature subset, nothing else), with one or
+// two distant lights, and akGrid sampling with m | 64 whose samples fill
+// whole 4-sample batches of every lane (spp a multiple of 256): every sample
+// is valid and a lane's samples share one column. Off with RT_FLAG_NO_LEAN1.
+// The general pixels of the same launches go to gen1_loop (off with
+// RT_FLAG_NO_GEN1).
+bool lean1_ok(const rt_scene* s, const FastParams& p, unsigned sub) {
+  return sub == SUB_MESH && p.nobj == 2 && p.shadow_mesh >= 0 &&
+         (p.nlight == 1 || p.nlight == 2) && !p.has_point_light && p.aa_kind == RT_AA_GRID &&
+         p.log2_grid_m >= 0 && p.log2_grid_m <= 6 && p.lanes_per_px == 64 && p.spp % 256 == 0 &&
+         p.iters * 64 == p.spp && p.iters % 4 == 0 && s->nobj == 2;
+}
+
+// The kernels of the call (Plan), from its mapping, its FastParams (the
+// scene's counts, the sampling, the light grids, the launch order) and the
+// flags. Two-class launch (one pixel per wave): the lean pixels — no camera
+// ray can hit the mesh, every light a distant light whose shadow rays from
+// the pixel provably miss it, no reflection — get a kernel of their own.
+void plan_kernels(const rt_scene* s, const rt_options* o, const Mapping& mp, const FastParams& p, Plan& pl) {
+  const uint32_t fl = o->flags;
+  pl.build = !(fl & RT_FLAG_NO_BINNING) && pl.L >= 16 && sampler_in_pixel(o->aa_kind);
+  pl.records = pl.L == 64;
+  pl.want_split = !(fl & (RT_FLAG_NO_SPLIT | RT_FLAG_COUNT_TRAVERSAL)) && !p.cost && !cost_dump_path() && s->nlight <= 8;
+  if (pl.build && pl.records && pl.want_split && !p.order) pl.lean_bpc = rtmi_lean_f32_blocks_per_cu(pl.sub, pl.shmem);
+  pl.two_class = pl.lean_bpc > 0;
+  pl.lp = 64;
+  if (pl.two_class) {
+    pl.one_plane = lean1_ok(s, p, pl.sub);
+    if (!(fl & RT_FLAG_NO_BATCH) && p.shadow_mesh >= 0 && p.grids && !p.has_point_light)
+      pl.gen_bpc = rtmi_gen_f32_blocks_per_cu(pl.sub, pl.shmem);
+    pl.gen = pl.gen_bpc > 0;
+    pl.gen1 = pl.gen && pl.one_plane && !(fl & RT_FLAG_NO_GEN1);
+    pl.lean1 = pl.one_plane && !(fl & RT_FLAG_NO_LEAN1);
+    int lean1q4_bpc = 0;
+    if (pl.lean1) {
+      // 16 pixels per item (lp = 4) unless the launch's groups make fewer
+      // items than resident waves (a short launch, e.g. a scanline), then 4
+      // (lp = 16). (Round 3 switched below 8 items per wave; a rank's bands at
+      // N = 8 — 2 per wave — render faster at 16 pixels per item in a
+      // back-to-back loop: 0.1605 -> 0.1539 ms, N = 4 0.278 -> 0.265 ms,
+      // profiles/r4/ab/r4t_*)
+      lean1q4_bpc = rtmi_lean1_f32_blocks_per_cu(p.nlight, 4);
+      const long long lwaves4 = 4LL * std::min<long long>((long long)lean1q4_bpc * s->num_cus, s->max_waves / 4);
+      pl.lp = (long long)(p.ngroups + 15) / 16 >= lwaves4 ? 4 : 16;
+    }
+    // one-plane launches: both lists in one kernel (k_render_mix1: the
+    // general items first, then the lean ones) — one ramp and one tail
+    pl.mix = pl.gen1 && pl.lean1 && !(fl & RT_FLAG_NO_MIX);
+    const bool idx_fits = (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
+    pl.uniform = pl.lean1 && !(fl & RT_FLAG_NO_UNIFORM) && idx_fits;
+    pl.ground = pl.gen1 && !(fl & RT_FLAG_NO_GROUND1) && idx_fits;
+    if (pl.mix) {
+      pl.mix_bpc = rtmi_mix1_f32_blocks_per_cu(p.nlight, pl.lp);
+    } else {
+      if (pl.gen1) pl.gen1_bpc = rtmi_gen1_f32_blocks_per_cu(p.nlight);
+      pl.lean_list_bpc = !pl.lean1    ? pl.lean_bpc
+                         : pl.lp == 4 ? lean1q4_bpc
+                                      : rtmi_lean1_f32_blocks_per_cu(p.nlight, pl.lp);
+    }
+  } else {
+    // RT_FLAG_COMPACT, reflective scenes: reflected rays compacted per wave
+    // (k_render_wave); not for an instrumented launch or a progressive
+    // pass that fills step x step blocks (its pixels' sums are stored
+    // more than once)
+    const long long span = (long long)mp.nrows * o->width;
+    if ((pl.sub & SUB_REFLECT) && (fl & RT_FLAG_COMPACT) && !(fl & RT_FLAG_COUNT_TRAVERSAL) &&
+        !(mp.mode == 0 && mp.step > 1) && span < (1ll << 27))
+      pl.wave_bpc = rtmi_wave_f32_blocks_per_cu(pl.sub, pl.shmem);
+    pl.wave = pl.wave_bpc > 0;
+  }
+}
+
+// The float32 launch's parameters and plan, and this call's camera-dependent
+// data built on the device (rt_frame.h) in stream order before the render
 // kernels: the mesh's camera-ray lists (>= 16 samples per pixel), the object
-// masks, and for one-pixel waves the pixel records — with *split, also the
-// lean / general lists of a two-class launch.
+// masks, and for one-pixel waves the pixel records — with pl.two_class, also
+// the lean / general lists of a two-class launch (*split: they exist).
 // zero / nzero: the render kernels' queue heads + Stats words; a call that
 // builds pixel lists zeroes them in its first build launch (*zeroed), else
 // the caller clears them.
-int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, FastParams& p, int* blocks,
+int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, FastParams& p, Plan& pl,
               rt_scene::Order** measuring, hipStream_t st, bool* split, unsigned int* zero, int nzero, bool* zeroed) {
   std::memset(&p, 0, sizeof p);
   p.objs = s->f32.objs.p;
@@ -552,7 +678,7 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   p.band_h = mp.band_h;
   p.rank = mp.rank;
   p.world = mp.world;
-  const Plan pl = plan_mapping(s, o, mp, spp);
+  pl = plan_mapping(s, o, mp, spp);
   p.lanes_per_px = pl.L;
   p.log2_lanes = pl.log2L;
   p.tile_x = pl.tx;
@@ -615,23 +741,13 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   p.order = ou.order;
   p.cost = ou.cost;
   *measuring = ou.entry;
-  *blocks = pl.blocks;
   *split = false;
   *zeroed = false;
-  if (!binning || pl.L < 16 || !sampler_in_pixel(o->aa_kind)) return RT_OK;
+  plan_kernels(s, o, mp, p, pl);
+  if (!pl.build) return RT_OK;
   // this call's camera-dependent data (nothing of it is kept from earlier calls)
   int rc;
   bool lists = false, masks = false;
-  // two-class launch (one pixel per wave): the lean pixels — no camera ray
-  // can hit the mesh, every light a distant light whose shadow rays from the
-  // pixel provably miss it, no reflection — get a kernel of their own; not
-  // for the measuring launch of a launch order or instrumented launches
-  static const char* cost_dump = rtmi::diag_env("RTMI_COST_DUMP");
-  const unsigned sub = f32_subset(s, o);
-  const bool want_split = !(o->flags & (RT_FLAG_NO_SPLIT | RT_FLAG_COUNT_TRAVERSAL)) && !p.cost && !cost_dump &&
-                          s->nlight <= 8 && rtmi_lean_f32_blocks_per_cu(sub, f32_table_lds(s, o)) > 0;
-  const bool records = pl.L == 64;  // one-pixel groups: records (+ the split)
-  *split = records && want_split && !p.order;
   // the build on the scene's build stream after the call two back (the last
   // user of this buffer set), joined into the caller's stream before the
   // render kernels: it overlaps the previous call's render
@@ -647,18 +763,7 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
     }
     return RT_OK;
   };
-  // the lean pixels' uniform classes: when the lean list goes to lean1q_loop
-  // (launch() below takes the same decisions), off with RT_FLAG_NO_UNIFORM;
-  // the class sits above the group index in a list entry
-  const bool uniform = *split && lean1_ok(s, o, p, sub) && !(o->flags & (RT_FLAG_NO_LEAN1 | RT_FLAG_NO_UNIFORM)) &&
-                       rtmi_lean1_quads() && (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
-  // the general pixels' ground class: when the general list goes to
-  // gen1_loop (launch() below: gen1), off with RT_FLAG_NO_GROUND1
-  const bool ground = *split && lean1_ok(s, o, p, sub) &&
-                      !(o->flags & (RT_FLAG_NO_BATCH | RT_FLAG_NO_GEN1 | RT_FLAG_NO_GROUND1)) && p.grids &&
-                      rtmi_gen_f32_blocks_per_cu(sub, f32_table_lds(s, o)) > 0 &&
-                      (long long)mp.ncols * mp.nrows <= (long long)kLeanIdxMask;
-  if ((rc = frame_build(s, o, mp, p, records, *split, uniform, ground, zero, nzero, bs, &lists, zeroed))) {
+  if ((rc = frame_build(s, o, mp, p, pl.records, pl.two_class, pl.uniform, pl.ground, zero, nzero, bs, &lists, zeroed))) {
     join();
     return rc;
   }
@@ -666,9 +771,8 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
     p.pix_slots = s->fr.slots.p;
     p.pix_cnt = s->fr.info.p;
     p.slot_lg = s->fr.slot_lg;
-    if (records) p.pix_info = s->fr.info.p;
-  } else {
-    *split = false;
+    if (pl.records) p.pix_info = s->fr.info.p;
+    *split = pl.two_class;
   }
   if (s->objbins) {
     if ((rc = frame_obj_masks(s, o, mp, bs, &masks))) {
@@ -759,26 +863,204 @@ void fill_params(rt_scene* s, const PrecisionData<R>& pd, const rt_options* o, c
   *blocks = (int)std::max(1LL, std::min<long long>(want, cap));
 }
 
-// k_render_lean1 (rt_fast.h) renders the lean pixels when the scene's only
-// analytic object is one plane and every transform a translation (the
-// mesh + plane feature subset, nothing else), with one or two distant lights,
-// and akGrid sampling with m | 64 whose samples fill whole 4-sample batches
-// of every lane (spp a multiple of 256): every sample is valid and a lane's
-// samples share one column. Off with RT_FLAG_NO_LEAN1. The general pixels of
-// the same launches go to k_render_gen1 (off with RT_FLAG_NO_GEN1).
-// Whether a one-plane two-class launch runs as one merged kernel
-// (k_render_mix1). RTMI_MIX=0/1 forces it (diagnostic A/B); by default:
-// always.
-bool mix_policy() {
-  static const int force = rtmi::diag_env("RTMI_MIX") ? std::atoi(rtmi::diag_env("RTMI_MIX")) : -1;
-  return force != 0;
+// The float64 call: its pixel records (when the scene has skip planes), then
+// k_render_px64 or k_render. *launched: blocks of the render kernel.
+int launch_f64(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, int* launched) {
+  RenderParams<double> p;
+  int blocks = 1;
+  fill_params<double>(s, s->f64, o, mp, d_out, p, &blocks);
+  s->last_general = p.ngroups;
+  if (p.ngroups == 0) return RT_OK;
+  if (p.aa_kind >= RT_AA_JITTERED) {
+    const size_t need = (size_t)blocks * 256 * 2 * (size_t)p.spp;
+    if (s->f64_tables.n < need) {
+      HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffer
+      int rc = s->f64_tables.alloc(need);
+      if (rc) return rc;
+    }
+    p.sample_scratch = s->f64_tables.p;
+  }
+  // this call's pixel records (the float32 path's build, one launch set):
+  // a pixel whose camera rays provably miss the mesh skips their traversal,
+  // and its shadow rays to the lights its skip bits clear skip theirs —
+  // the same answers (the traversal would find no face), so frames and
+  // Stats stay bit-exact (tests/test_gpu_parity.py)
+  const bool binning = !(o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_COUNT_TRAVERSAL));
+  bool lists = false;
+  if (binning && sampler_in_pixel(o->aa_kind) && s->skippable) {
+    FastParams pf;
+    std::memset(&pf, 0, sizeof pf);
+    bool zeroed = false;
+    if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
+    if (lists) p.pix_info = s->fr.info.p;
+  }
+  // one pixel per wave (k_render_px64): akGrid with >= 64 samples per
+  // pixel; the camera rays search this call's pixel lists, the shadow rays
+  // to distant lights the scene's light grids (rt_device.h mesh_lists)
+  const int px64 = o->aa_kind == RT_AA_GRID && p.spp >= 64 && !(o->flags & (RT_FLAG_F64_PER_LANE | RT_FLAG_COUNT_TRAVERSAL))
+                       ? (s->any_reflective && o->max_ray_depth >= 1 ? 2 : 1)
+                       : 0;
+  if (px64) {
+    if (lists) {
+      p.pix_slots = s->fr.slots.p;
+      p.slot_lg = s->fr.slot_lg;
+      p.lean_plane = s->lean64_plane;
+    }
+    if (binning && s->has_grids) {
+      p.grids = s->grids.p;
+      p.grid_off = s->grid_off.p;
+      p.grid_ent = s->grid_ent.p;
+      if (!s->sh64_ready && s->shadow_mesh >= 0) {
+        if (int rc = s->sh64.alloc(s->grid_ent.n)) return rc;
+        for (int li = 0; li < s->nlight && li < (int)s->grid_host.size(); ++li) {
+          const LightGrid& g = s->grid_host[(size_t)li].g;  // (the header and the count survive a relight)
+          const int64_t ne = s->grid_nent[(size_t)li];
+          if (g.gu <= 0 || ne <= 0) continue;
+          const int e = rtmi_build_sh64(s->f64.objects.p, s->shadow_mesh, s->f64.lights.p, li,
+                                        s->grid_ent.p + g.ent_base, (int)ne, s->f64.tris.p,
+                                        (int32_t)s->num_nodes, s->sh64.p + g.ent_base, st);
+          if (e) return fail(RT_E_DEVICE, "shadow record build failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        s->sh64_ready = true;
+      }
+      if (s->sh64_ready) p.sh64 = s->sh64.p;
+    }
+    p.tri_rec0 = (int32_t)s->num_nodes;
+    const long long nbatch = ((long long)mp.nrows * mp.ncols + rtmi_px64_batch() - 1) / rtmi_px64_batch();
+    const long long resident = (long long)std::max(1, rtmi_px64_blocks_per_cu(px64)) * s->num_cus;
+    blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
+  }
+  if (o->flags & RT_FLAG_TIMING) HIP_TRY(hipEventRecord(s->tev[1], st));  // after the per-call build
+  const int e = rtmi_launch_render_f64(&p, blocks, px64, st);
+  if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  *launched = blocks;
+  return RT_OK;
 }
 
-bool lean1_ok(const rt_scene* s, const rt_options* o, const FastParams& p, unsigned sub) {
-  return sub == SUB_MESH && p.nobj == 2 && p.shadow_mesh >= 0 &&
-         (p.nlight == 1 || p.nlight == 2) && !p.has_point_light && p.aa_kind == RT_AA_GRID &&
-         p.log2_grid_m >= 0 && p.log2_grid_m <= 6 && p.lanes_per_px == 64 && p.spp % 256 == 0 &&
-         p.iters * 64 == p.spp && p.iters % 4 == 0 && s->nobj == 2;
+// Two-class launch: the general kernel on its list and the lean kernel on its
+// own, as one merged kernel (pl.mix) or on two streams. The lists and their
+// entry counts come from this call's k_frame_build2 (the host never reads
+// them: grids and items are sized for the launch's groups, the kernels stop
+// at the device counts). *launched: blocks of all its kernels.
+int launch_two_class(rt_scene* s, const Plan& pl, const FastParams& p, hipStream_t st, int* launched) {
+  int32_t* const n_heavy = s->fr.ctr.p + FC_HEAVY;
+  int32_t* const n_lean = s->fr.ctr.p + FC_LEAN;
+  const int lp = pl.lp;
+  FastParams ph = p, pn = p;
+  // the general pixels: the batched kernel (k_render_gen) for scenes of one
+  // mesh object with distant lights only, no reflection (the lean kernel's
+  // subsets) when both camera lists and light grids exist
+  ph.order = s->fr.heavy.p;
+  ph.ngroups = p.ngroups;
+  ph.list_n = n_heavy;
+  // the lean pixels' work items: runs of kLeanRun pixels (k_render_lean),
+  // 64 / lp pixels (k_render_lean1q, lp lanes per pixel)
+  const int lrun = lp == 64 ? kLeanRun : 64 / lp;
+  const int lruns = (p.ngroups + lrun - 1) / lrun;  // at most: the kernels stop at the device count
+  pn.order = s->fr.lean.p;
+  pn.ngroups = lruns;
+  pn.list_n = n_lean;
+  pn.stat_flush = std::max(1, p.stat_flush / lrun);
+  pn.queue = s->queue.p + (size_t)kQueueShards * kQueueStride;
+  if (pl.mix) {
+    FastParams pm = ph;
+    pm.order2 = pn.order;
+    pm.ngroups2 = pn.ngroups;
+    pm.list_n2 = n_lean;
+    pm.stat_flush = std::min(ph.stat_flush, pn.stat_flush);
+    const long long mcap = (long long)pl.mix_bpc * s->num_cus;
+    const int mb = (int)std::max(1LL, std::min<long long>(std::min<long long>(mcap, pl.blocks),
+                                                          ((long long)p.ngroups + lruns + 3) / 4));
+    pm.shards = std::min(kQueueShards, mb);
+    pm.shards2 = pm.shards;
+    const int e = rtmi_launch_mix1_f32(&pm, p.nlight, lp, mb, st);
+    if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    *launched = mb;
+    s->last_lean_kind = 3 | (3 << 2) | (lp << 8);
+    s->last_batched = -1;  // = the general list (device count)
+    return RT_OK;
+  }
+  const long long hcap =
+      pl.gen ? std::min<long long>((long long)(pl.gen1 ? pl.gen1_bpc : pl.gen_bpc) * s->num_cus, pl.blocks) : pl.blocks;
+  const int hb = (int)std::max(1LL, std::min<long long>(hcap, ((long long)p.ngroups + 3) / 4));
+  ph.shards = std::min(kQueueShards, hb);
+  const long long lcap = (long long)pl.lean_list_bpc * s->num_cus;
+  const int lb = (int)std::max(1LL, std::min<long long>(std::min<long long>(lcap, s->max_waves / 4),
+                                                        ((long long)lruns + 3) / 4));
+  pn.shards = std::min(kQueueShards, lb);
+  pn.partials = s->partials.p + (size_t)hb * 4 * kStatSlots;
+  // general kernel first on the caller's stream, the lean kernel on the
+  // scene's aux stream (forked after the caller's earlier work, joined
+  // before its later work)
+  HIP_TRY(hipEventRecord(s->fork, st));
+  HIP_TRY(hipStreamWaitEvent(s->aux, s->fork, 0));
+  int e = pl.gen1  ? rtmi_launch_gen1_f32(&ph, p.nlight, hb, st)
+          : pl.gen ? rtmi_launch_gen_f32(&ph, pl.sub, hb, pl.shmem, st)
+                   : rtmi_launch_render_f32(&ph, pl.sub, hb, pl.shmem, st);
+  if (!e)
+    e = pl.lean1 ? rtmi_launch_lean1_f32(&pn, p.nlight, lp, lb, s->aux)
+                 : rtmi_launch_lean_f32(&pn, pl.sub, lb, pl.shmem, s->aux);
+  if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipEventRecord(s->join, s->aux));
+  HIP_TRY(hipStreamWaitEvent(st, s->join, 0));
+  *launched = hb + lb;
+  s->last_lean_kind = (pl.lean1 ? 2 : 1) | ((pl.gen1 ? 2 : pl.gen ? 1 : 0) << 2) | (lp << 8);
+  s->last_batched = pl.gen ? -1 : 0;
+  return RT_OK;
+}
+
+// One-kernel launch: every group general — k_render_wave (pl.wave: reflected
+// rays compacted per wave, then added to the framebuffer) or k_render_fast.
+int launch_one_kernel(rt_scene* s, const rt_options* o, const Mapping& mp, const Plan& pl, FastParams& p, float* d_out,
+                      hipStream_t st, int* launched) {
+  if (!pl.wave) {
+    const int e = rtmi_launch_render_f32(&p, pl.sub, pl.blocks, pl.shmem, st);
+    if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    *launched = pl.blocks;
+    return RT_OK;
+  }
+  const long long span = (long long)mp.nrows * o->width;
+  const int wb = (int)std::max(1LL, std::min<long long>(std::min<long long>((long long)pl.wave_bpc * s->num_cus,
+                                                                            s->max_waves / 4),
+                                                        ((long long)p.ngroups + 3) / 4));
+  const size_t qfl = (size_t)wb * 4 * kReflQueue * kReflFields;
+  const size_t nsec = (size_t)span * 3;
+  if (s->refl_queue.n < qfl || s->refl_sec.n < nsec) {
+    HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffers
+    int rc = s->refl_queue.n < qfl ? s->refl_queue.alloc(qfl) : RT_OK;
+    if (!rc && s->refl_sec.n < nsec) rc = s->refl_sec.alloc(nsec);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemsetAsync(s->refl_sec.p, 0, nsec * sizeof(long long), st));
+  p.rq = s->refl_queue.p;
+  p.sec = s->refl_sec.p;
+  p.sec_base = mp.mode == 0 ? (int64_t)mp.y0 * o->width : 0;
+  p.shards = std::min(kQueueShards, wb);
+  int e = rtmi_launch_wave_f32(&p, pl.sub, wb, pl.shmem, st);
+  if (!e)
+    e = rtmi_launch_sec_add(d_out + (size_t)p.sec_base * 3, p.sec, nsec, o->aa_kind != RT_AA_NONE ? p.inv_len : 1.0f,
+                            s->num_cus, st);
+  if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  *launched = wb;
+  s->last_lean_kind = 16;
+  return RT_OK;
+}
+
+// After the render kernels of a float32 launch: the measuring launch of a
+// launch order is marked, a cost dump written.
+int launch_tail(hipStream_t st, int ngroups, rt_scene::Order* measuring, DevBuf<unsigned>& dbg_cost) {
+  if (measuring) HIP_TRY(hipEventRecord(measuring->measured, st));
+  if (dbg_cost.p) {
+    std::vector<unsigned> c((size_t)ngroups);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(c.data(), dbg_cost.p, c.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    dbg_cost.release();
+    if (FILE* f = std::fopen(cost_dump_path(), "wb")) {
+      std::fwrite(c.data(), sizeof(unsigned), c.size(), f);
+      std::fclose(f);
+    }
+  }
+  return RT_OK;
 }
 
 // zero / nzero: the queue heads and / or Stats words every call clears
@@ -786,7 +1068,6 @@ bool lean1_ok(const rt_scene* s, const rt_options* o, const FastParams& p, unsig
 // them in its first build launch: one launch fewer).
 int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, bool reduce,
            unsigned int* zero, int nzero) {
-  int blocks = 1;
   auto clear = [&]() -> int {
     if (nzero > 0) HIP_TRY(hipMemsetAsync(zero, 0, (size_t)nzero * sizeof(unsigned int), st));
     return RT_OK;
@@ -802,270 +1083,33 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
   s->last_lean_kind = 0;
   s->last_general = 0;
   s->last_batched = 0;
+  int launched = 0;  // blocks of the render kernels (0: nothing to render)
   if (o->precision == RT_FP64) {
     if (int rc = clear()) return rc;
-    RenderParams<double> p;
-    fill_params<double>(s, s->f64, o, mp, d_out, p, &blocks);
-    s->last_general = p.ngroups;
-    if (p.ngroups == 0) return RT_OK;
-    if (p.aa_kind >= RT_AA_JITTERED) {
-      const size_t need = (size_t)blocks * 256 * 2 * (size_t)p.spp;
-      if (s->f64_tables.n < need) {
-        HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffer
-        int rc = s->f64_tables.alloc(need);
-        if (rc) return rc;
-      }
-      p.sample_scratch = s->f64_tables.p;
-    }
-    s->last_lean = 0;
-    s->last_lean_kind = 0;
-    s->last_general = p.ngroups;
-    s->last_batched = 0;
-    // this call's pixel records (the float32 path's build, one launch set):
-    // a pixel whose camera rays provably miss the mesh skips their traversal,
-    // and its shadow rays to the lights its skip bits clear skip theirs —
-    // the same answers (the traversal would find no face), so frames and
-    // Stats stay bit-exact (tests/test_gpu_parity.py)
-    const bool binning = !(o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_COUNT_TRAVERSAL));
-    bool lists = false;
-    if (binning && sampler_in_pixel(o->aa_kind) && s->skippable) {
-      FastParams pf;
-      std::memset(&pf, 0, sizeof pf);
-      bool zeroed = false;
-      if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
-      if (lists) p.pix_info = s->fr.info.p;
-    }
-    // one pixel per wave (k_render_px64): akGrid with >= 64 samples per
-    // pixel; the camera rays search this call's pixel lists, the shadow rays
-    // to distant lights the scene's light grids (rt_device.h mesh_lists)
-    const int px64 = o->aa_kind == RT_AA_GRID && p.spp >= 64 && !(o->flags & (RT_FLAG_F64_PER_LANE | RT_FLAG_COUNT_TRAVERSAL))
-                         ? (s->any_reflective && o->max_ray_depth >= 1 ? 2 : 1)
-                         : 0;
-    if (px64) {
-      if (lists) {
-        p.pix_slots = s->fr.slots.p;
-        p.slot_lg = s->fr.slot_lg;
-        p.lean_plane = s->lean64_plane;
-      }
-      if (binning && s->has_grids) {
-        p.grids = s->grids.p;
-        p.grid_off = s->grid_off.p;
-        p.grid_ent = s->grid_ent.p;
-        if (!s->sh64_ready && s->shadow_mesh >= 0) {
-          if (int rc = s->sh64.alloc(s->grid_ent.n)) return rc;
-          for (int li = 0; li < s->nlight && li < (int)s->grid_host.size(); ++li) {
-            const LightGrid& g = s->grid_host[(size_t)li].g;  // (the header and the count survive a relight)
-            const int64_t ne = s->grid_nent[(size_t)li];
-            if (g.gu <= 0 || ne <= 0) continue;
-            const int e = rtmi_build_sh64(s->f64.objects.p, s->shadow_mesh, s->f64.lights.p, li,
-                                          s->grid_ent.p + g.ent_base, (int)ne, s->f64.tris.p,
-                                          (int32_t)s->num_nodes, s->sh64.p + g.ent_base, st);
-            if (e) return fail(RT_E_DEVICE, "shadow record build failed: %s", hipGetErrorString((hipError_t)e));
-          }
-          s->sh64_ready = true;
-        }
-        if (s->sh64_ready) p.sh64 = s->sh64.p;
-      }
-      p.tri_rec0 = (int32_t)s->num_nodes;
-      const long long nbatch = ((long long)mp.nrows * mp.ncols + rtmi_px64_batch() - 1) / rtmi_px64_batch();
-      const long long resident = (long long)std::max(1, rtmi_px64_blocks_per_cu(px64)) * s->num_cus;
-      blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
-    }
-    if (o->flags & RT_FLAG_TIMING) HIP_TRY(hipEventRecord(s->tev[1], st));  // after the per-call build
-    const int e = rtmi_launch_render_f64(&p, blocks, px64, st);
-    if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int rc = launch_f64(s, o, mp, d_out, st, &launched)) return rc;
   } else {
+    if (mp.nrows == 0 || mp.ncols == 0) return clear();
     FastParams p;
+    Plan pl;
     rt_scene::Order* measuring = nullptr;
     bool split = false, zeroed = false;
-    if (mp.nrows == 0 || mp.ncols == 0) return clear();
-    int rc = fill_fast(s, o, mp, d_out, p, &blocks, &measuring, st, &split, zero, nzero, &zeroed);
+    int rc = fill_fast(s, o, mp, d_out, p, pl, &measuring, st, &split, zero, nzero, &zeroed);
     if (rc) return rc;
     if (!zeroed && (rc = clear())) return rc;
     if (o->flags & RT_FLAG_TIMING) HIP_TRY(hipEventRecord(s->tev[1], st));
     s->last_general = p.ngroups;
     if (p.ngroups == 0) return RT_OK;
-    // diagnostic (tools/cost_map.py): RTMI_COST_DUMP=<file> records every
-    // pixel group's duration (s_memtime cycles) of this launch into <file>
-    static const char* cost_dump = rtmi::diag_env("RTMI_COST_DUMP");
     DevBuf<unsigned> dbg_cost;
-    if (cost_dump && !measuring && !p.cost) {
+    if (cost_dump_path() && !measuring && !p.cost) {
       if (dbg_cost.alloc((size_t)p.ngroups) == RT_OK) p.cost = dbg_cost.p;
     }
     s->fr.counted = split;
-    if (split) {  // two-class launch: the general kernel on its list, then the lean kernel on its own
-      // the lists and their entry counts come from this call's k_frame_build2
-      // (the host never reads them: grids and items are sized for the launch's
-      // groups, the kernels stop at the device counts)
-      int32_t* const n_heavy = s->fr.ctr.p + FC_HEAVY;
-      int32_t* const n_lean = s->fr.ctr.p + FC_LEAN;
-      const size_t shmem = f32_table_lds(s, o);
-      const unsigned sub = f32_subset(s, o);
-      FastParams ph = p, pl = p;
-      // the general pixels: the batched kernel (k_render_gen) for scenes of
-      // one mesh object with distant lights only, no reflection (the lean
-      // kernel's subsets) when both camera lists and light grids exist
-      const int gbpc = (o->flags & RT_FLAG_NO_BATCH) || p.shadow_mesh < 0 || !p.pix_slots || !p.grids ||
-                               p.has_point_light
-                           ? 0
-                           : rtmi_gen_f32_blocks_per_cu(sub, shmem);
-      const bool gen = gbpc > 0;
-      const bool one_plane = lean1_ok(s, o, p, sub);
-      const bool gen1 = gen && one_plane && !(o->flags & RT_FLAG_NO_GEN1);
-      const long long hcap =
-          gen ? std::min<long long>((long long)(gen1 ? rtmi_gen1_f32_blocks_per_cu(p.nlight) : gbpc) * s->num_cus, blocks)
-              : blocks;
-      // diagnostic: RTMI_GEN_WAVES_CAP / RTMI_LEAN_WAVES_CAP = resident waves per SIMD each kernel may take
-      static const int gen_cap = rtmi::diag_env("RTMI_GEN_WAVES_CAP") ? std::atoi(rtmi::diag_env("RTMI_GEN_WAVES_CAP")) : 0;
-      static const int lean_cap = rtmi::diag_env("RTMI_LEAN_WAVES_CAP") ? std::atoi(rtmi::diag_env("RTMI_LEAN_WAVES_CAP")) : 0;
-      const long long hcap2 = gen_cap > 0 ? std::min<long long>(hcap, (long long)gen_cap * s->num_cus) : hcap;
-      const int hb = (int)std::max(1LL, std::min<long long>(hcap2, ((long long)p.ngroups + 3) / 4));
-      ph.order = s->fr.heavy.p;
-      ph.ngroups = p.ngroups;
-      ph.list_n = n_heavy;
-      ph.shards = std::min(kQueueShards, hb);
-      const bool lean1 = one_plane && !(o->flags & RT_FLAG_NO_LEAN1);
-      // work items: runs of kLeanRun pixels (k_render_lean, k_render_lean1),
-      // 64 / lp pixels (k_render_lean1q, lp lanes per pixel): 16 per item
-      // unless the launch's groups make fewer items than resident waves (a
-      // short launch, e.g. a scanline), then 4. (Round 3 switched below 8
-      // items per wave; a rank's bands at N = 8 — 2 per wave — render faster
-      // at 16 pixels per item in a back-to-back loop: 0.1605 -> 0.1539 ms,
-      // N = 4 0.278 -> 0.265 ms, profiles/r4/ab/r4t_*)
-      const long long lwaves4 =
-          4LL * std::min<long long>((long long)rtmi_lean1_f32_blocks_per_cu(p.nlight, 4) * s->num_cus, s->max_waves / 4);
-      static const int lp_env = rtmi::diag_env("RTMI_LEAN_LP") ? std::atoi(rtmi::diag_env("RTMI_LEAN_LP")) : 0;  // diagnostic: 4 / 16
-      const int lp = !(lean1 && rtmi_lean1_quads())
-                         ? 64
-                         : (lp_env == 4 || lp_env == 16 ? lp_env : ((long long)(p.ngroups + 15) / 16 >= lwaves4 ? 4 : 16));
-      const long long lcap =
-          (long long)(lean1 ? rtmi_lean1_f32_blocks_per_cu(p.nlight, lp) : rtmi_lean_f32_blocks_per_cu(sub, shmem)) *
-          s->num_cus;
-      const int lrun = lp == 64 ? kLeanRun : 64 / lp;
-      const int lruns = (p.ngroups + lrun - 1) / lrun;  // at most: the kernels stop at the device count
-      const long long lcap2 = lean_cap > 0 ? std::min<long long>(lcap, (long long)lean_cap * s->num_cus) : lcap;
-      const int lb = (int)std::max(1LL, std::min<long long>(std::min<long long>(lcap2, s->max_waves / 4),
-                                                            ((long long)lruns + 3) / 4));
-      pl.order = s->fr.lean.p;
-      pl.ngroups = lruns;
-      pl.list_n = n_lean;
-      pl.stat_flush = std::max(1, p.stat_flush / lrun);
-      pl.shards = std::min(kQueueShards, lb);
-      pl.queue = s->queue.p + (size_t)kQueueShards * kQueueStride;
-      pl.partials = s->partials.p + (size_t)hb * 4 * kStatSlots;
-      // one-plane launches: both lists in one kernel (k_render_mix1: the
-      // general items first, then the lean ones) — one ramp and one tail
-      const bool mix = gen1 && lean1 && lp != 64 && !(o->flags & RT_FLAG_NO_MIX) && mix_policy();
-      if (mix) {
-        FastParams pm = ph;
-        pm.order2 = pl.order;
-        pm.ngroups2 = pl.ngroups;
-        pm.list_n2 = n_lean;
-        pm.stat_flush = std::min(ph.stat_flush, pl.stat_flush);
-        const long long mcap = (long long)rtmi_mix1_f32_blocks_per_cu(p.nlight, lp) * s->num_cus;
-        const int mb = (int)std::max(1LL, std::min<long long>(std::min<long long>(mcap, blocks),
-                                                              ((long long)p.ngroups + lruns + 3) / 4));
-        static const int shard_cap = rtmi::diag_env("RTMI_SHARDS") ? std::atoi(rtmi::diag_env("RTMI_SHARDS")) : 0;  // diagnostic
-        pm.shards = std::min(shard_cap > 0 ? std::min(shard_cap, kQueueShards) : kQueueShards, mb);
-        pm.shards2 = pm.shards;
-        // diagnostic (RTMI_PIPE_GRID=<percent>): a pipelined call's grid capped,
-        // leaving CU slots to the next call's build
-        static const int pipe_grid = rtmi::diag_env("RTMI_PIPE_GRID") ? std::atoi(rtmi::diag_env("RTMI_PIPE_GRID")) : 0;
-        const int mbl = s->pipe && pipe_grid > 0 ? std::max(1, (int)((long long)mb * pipe_grid / 100)) : mb;
-        const int e = rtmi_launch_mix1_f32(&pm, p.nlight, lp, mbl, st);
-        if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        blocks = mb;
-        s->last_lean_kind = 3 | (3 << 2) | (lp << 8);
-        s->last_batched = -1;  // = the general list (device count)
-        goto launched;
-      }
-      // general kernel first on the caller's stream, the lean kernel on
-      // the scene's aux stream (forked after the caller's earlier work,
-      // joined before its later work)
-      static const bool serial = rtmi::diag_env("RTMI_SPLIT_SERIAL") != nullptr;  // diagnostic: one stream
-      hipStream_t sl = serial ? st : s->aux;
-      if (!serial) {
-        HIP_TRY(hipEventRecord(s->fork, st));
-        HIP_TRY(hipStreamWaitEvent(s->aux, s->fork, 0));
-      }
-      static const bool lean_first = rtmi::diag_env("RTMI_LEAN_FIRST") != nullptr;  // diagnostic
-      auto launch_lean = [&]() {
-        return lean1 ? rtmi_launch_lean1_f32(&pl, p.nlight, lp, lb, sl) : rtmi_launch_lean_f32(&pl, sub, lb, shmem, sl);
-      };
-      int e = lean_first ? launch_lean() : 0;
-      if (!e)
-        e = gen1  ? rtmi_launch_gen1_f32(&ph, p.nlight, hb, st)
-            : gen ? rtmi_launch_gen_f32(&ph, sub, hb, shmem, st)
-                  : rtmi_launch_render_f32(&ph, sub, hb, shmem, st);
-      if (!e && !lean_first) e = launch_lean();
-      if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      if (!serial) {
-        HIP_TRY(hipEventRecord(s->join, s->aux));
-        HIP_TRY(hipStreamWaitEvent(st, s->join, 0));
-      }
-      blocks = hb + lb;
-      s->last_lean_kind = (lean1 ? 2 : 1) | ((gen1 ? 2 : gen ? 1 : 0) << 2) | (lp << 8);
-      s->last_batched = gen ? -1 : 0;
-    } else {
-      s->last_lean = 0;
-      s->last_lean_kind = 0;
-      s->last_general = p.ngroups;
-      s->last_batched = 0;
-      const unsigned sub = f32_subset(s, o);
-      const size_t shmem = f32_table_lds(s, o);
-      // RT_FLAG_COMPACT, reflective scenes: reflected rays compacted per wave
-      // (k_render_wave); not for an instrumented launch or a progressive
-      // pass that fills step x step blocks (its pixels' sums are stored
-      // more than once)
-      const long long span = (long long)mp.nrows * o->width;
-      const int wbpc = (sub & SUB_REFLECT) && (o->flags & RT_FLAG_COMPACT) && !(o->flags & RT_FLAG_COUNT_TRAVERSAL) &&
-                               !(mp.mode == 0 && mp.step > 1) && span < (1ll << 27)
-                           ? rtmi_wave_f32_blocks_per_cu(sub, shmem)
-                           : 0;
-      if (wbpc > 0) {
-        const int wb = (int)std::max(1LL, std::min<long long>(std::min<long long>((long long)wbpc * s->num_cus,
-                                                                                  s->max_waves / 4),
-                                                              ((long long)p.ngroups + 3) / 4));
-        const size_t qfl = (size_t)wb * 4 * kReflQueue * kReflFields;
-        const size_t nsec = (size_t)span * 3;
-        if (s->refl_queue.n < qfl || s->refl_sec.n < nsec) {
-          HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffers
-          int rc2 = s->refl_queue.n < qfl ? s->refl_queue.alloc(qfl) : RT_OK;
-          if (!rc2 && s->refl_sec.n < nsec) rc2 = s->refl_sec.alloc(nsec);
-          if (rc2) return rc2;
-        }
-        HIP_TRY(hipMemsetAsync(s->refl_sec.p, 0, nsec * sizeof(long long), st));
-        p.rq = s->refl_queue.p;
-        p.sec = s->refl_sec.p;
-        p.sec_base = mp.mode == 0 ? (int64_t)mp.y0 * o->width : 0;
-        p.shards = std::min(kQueueShards, wb);
-        int e = rtmi_launch_wave_f32(&p, sub, wb, shmem, st);
-        if (!e)
-          e = rtmi_launch_sec_add(d_out + (size_t)p.sec_base * 3, p.sec, nsec, o->aa_kind != RT_AA_NONE ? p.inv_len : 1.0f,
-                                  s->num_cus, st);
-        if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        blocks = wb;
-        s->last_lean_kind = 16;
-      } else {
-        const int e = rtmi_launch_render_f32(&p, sub, blocks, shmem, st);
-        if (e) return fail(RT_E_DEVICE, "render kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      }
-    }
-  launched:
-    if (measuring) HIP_TRY(hipEventRecord(measuring->measured, st));
-    if (dbg_cost.p) {
-      std::vector<unsigned> c((size_t)p.ngroups);
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipMemcpy(c.data(), dbg_cost.p, c.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-      dbg_cost.release();
-      if (FILE* f = std::fopen(cost_dump, "wb")) {
-        std::fwrite(c.data(), sizeof(unsigned), c.size(), f);
-        std::fclose(f);
-      }
-    }
+    rc = split ? launch_two_class(s, pl, p, st, &launched) : launch_one_kernel(s, o, mp, pl, p, d_out, st, &launched);
+    if (rc) return rc;
+    if ((rc = launch_tail(st, p.ngroups, measuring, dbg_cost))) return rc;
   }
   // the per-wave rows are reduced when the Stats are read (flush_reduce)
-  if (reduce) s->pending_reduce = blocks * 4;
+  if (reduce && launched > 0) s->pending_reduce = launched * 4;
   return RT_OK;
 }
 
@@ -1092,10 +1136,8 @@ int read_stats(rt_scene* s, hipStream_t st, rt_stats* out) {
   // counts it, which is checked here.
   const unsigned long long rays = h[STAT_PRIMARY] + h[STAT_SHADOW] + h[STAT_REFL];
   const unsigned long long tests = (unsigned long long)s->nobj * rays;
-#if !(defined(RTMI_DIAG) && defined(RTMI_PX64_ONLY))  // that diagnostic skips samples on purpose
   if (h[STAT_TESTS] != 0 && h[STAT_TESTS] != tests)
     return fail(RT_E_DEVICE, "inconsistent intersection-test count (%llu vs %llu)", h[STAT_TESTS], tests);
-#endif
   out->num_intersection_tests = tests;
   out->num_intersection_hits = h[STAT_HITS];
   out->num_shadow_rays = h[STAT_SHADOW];

@@ -50,14 +50,6 @@ struct FastData {
   }
 };
 
-// Pixel-list slots per pixel, 2^lg: RTMI_SLOT_LG (A/B knob) or -1 = by image size.
-inline int slot_lg_env() {
-  static const int v = [] {
-    const char* e = rtmi::diag_env("RTMI_SLOT_LG");
-    return e ? std::min(10, std::max(0, std::atoi(e))) : -1;
-  }();
-  return v;
-}
 // by image size: the most slots (a power of two, 2^kSlotLg .. 256) whose
 // block stays within 2^27 entries
 inline int slot_lg_for(int w, int h) {
@@ -234,7 +226,7 @@ struct rt_scene {
     DevBuf<HugeFace> huge;
     DevBuf<unsigned char> tiles;   // per skip cell of a tile: shadow skips (k_frame_build1)
     int slot_lg = -1;              // slots allocated for 2^slot_lg entries per pixel (-1: none)
-    int want_lg = slot_lg_env();   // test hook (rtmi_test_slot_lg) / RTMI_SLOT_LG; -1: by image size
+    int want_lg = -1;              // test hook (rtmi_test_slot_lg); -1: by image size
     uint32_t calls = 0;            // build launches (their parity picks the huge-list counter)
     bool counted = false;          // the last launch's lean / general lists were counted on the device
     bool listed = false;           // the last launch built camera-ray lists

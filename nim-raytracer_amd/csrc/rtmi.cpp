@@ -291,16 +291,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     return fail(RT_E_INVALID, "null array with nonzero count");
   if (!affine(d->camera_to_world)) return fail(RT_E_UNSUPPORTED, "camera_to_world is not affine");
   const auto t0 = std::chrono::steady_clock::now();
-  // RTMI_SETUP_PROFILE=1: per-phase wall times of scene setup on stderr
-  static const bool profile = rtmi::diag_env("RTMI_SETUP_PROFILE") != nullptr;
-  auto tp = t0;
-  const auto mark = [&](const char* phase) {
-    if (!profile) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[rtmi setup] %-22s %9.3f ms\n", phase,
-                 std::chrono::duration<double, std::milli>(now - tp).count());
-    tp = now;
-  };
   if (int orc = check_objects(d->objects, d->num_objects, d->num_meshes)) return orc;
   for (int i = 0; i < d->num_lights; ++i)
     if (d->lights[i].type != RT_DISTANT_LIGHT && d->lights[i].type != RT_POINT_LIGHT)
@@ -364,12 +354,10 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
         if (x < bb[(size_t)k]) bb[(size_t)k] = x;
         if (x > bb[3 + (size_t)k]) bb[3 + (size_t)k] = x;
       }
-    mark("normals + bounds");
     int urc;
     if ((urc = d_verts[(size_t)m].upload(md.vertices, (size_t)md.num_vertices * 3)) ||
         (urc = d_faces[(size_t)m].upload(md.faces, (size_t)md.num_faces * 3)))
       return urc;
-    mark("mesh upload");
     const char* err = "BVH build failed";
     BvhBuildParams prm;
     // a face's vertices are finite under either builder (their min / max
@@ -397,7 +385,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
       ok = build_bvh(md.vertices, md.faces, md.num_faces, prm, &bvhs[(size_t)m], &err);
     }
     if (!ok) return fail(device_built ? RT_E_DEVICE : RT_E_INVALID, "mesh %d: %s", m, err);
-    mark("bvh build");
     node_base[(size_t)m] = (int32_t)all_nodes.size();
     for (BvhNode nd : bvhs[(size_t)m].nodes) {
       if (nd.n0 == 0 && nd.c0 >= 0) nd.c0 += node_base[(size_t)m];
@@ -442,10 +429,9 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   for (Event& e : s->tev) HIP_TRY(hipEventCreate(&e.h));
   {
     // the build stream at the highest priority (rank 0 of 8 back to back:
-    // 0.163 -> 0.161 ms); RTMI_PIPE_PRIO=0: the default priority (A/B)
+    // 0.163 -> 0.161 ms against the default priority)
     int lo = 0, hi = 0;
-    const char* pe = rtmi::diag_env("RTMI_PIPE_PRIO");
-    if (!(pe && std::atoi(pe) == 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
       HIP_TRY(hipStreamCreateWithPriority(&s->bstream.h, hipStreamNonBlocking, hi));
     else
       HIP_TRY(hipStreamCreateWithFlags(&s->bstream.h, hipStreamNonBlocking));
@@ -455,14 +441,9 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     // device: a device-scope release (no system-scope cache writeback) is
     // enough. `used` doubles as `done`, which the host waits on before
     // reading device memory and peers copy behind: system scope.
-    // RTMI_EVENT_SCOPE (A/B): 0 both system scope, 2 both device scope.
-    const char* es = rtmi::diag_env("RTMI_EVENT_SCOPE");
-    const int scope = es && *es ? std::atoi(es) : 1;
-    const unsigned fb = hipEventDisableTiming | (scope >= 1 ? hipEventReleaseToDevice : 0u);
-    const unsigned fu = hipEventDisableTiming | (scope >= 2 ? hipEventReleaseToDevice : 0u);
     for (rt_scene::Frame* f : {&s->fr, &s->fr2}) {
-      HIP_TRY(hipEventCreateWithFlags(&f->built.h, fb));
-      HIP_TRY(hipEventCreateWithFlags(&f->used.h, fu));
+      HIP_TRY(hipEventCreateWithFlags(&f->built.h, hipEventDisableTiming | hipEventReleaseToDevice));
+      HIP_TRY(hipEventCreateWithFlags(&f->used.h, hipEventDisableTiming));
     }
   }
   s->done = s->fr.used;
@@ -477,7 +458,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<DevMesh<float>> m;
     std::vector<float> n;
     fill_precision<float>(d, normals, bvhs, node_base, aabbs, o, l, m, nullptr, n);
-    mark("fp32 records");
     std::vector<FObj> fo;
     std::vector<FObjX> fx;
     std::vector<FMesh> fm;
@@ -491,7 +471,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
         (rc = s->f32.normals.upload(n)))
       return rc;
-    mark("fp32 upload");
   }
   {
     std::vector<DevObject<double>> o;
@@ -499,14 +478,12 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<DevMesh<double>> m;
     std::vector<double> n;
     fill_precision<double>(d, normals, bvhs, node_base, aabbs, o, l, m, nullptr, n);
-    mark("fp64 records");
     s->h_dm64 = m;
     int rc;
     if ((rc = s->f64.objects.upload(o)) || (rc = s->f64.meshes.upload(m)) ||
         (rc = s->f64.normals.upload(n)))
       return rc;
   }
-  mark("fp64 upload");
   {
     // triangle records in BVH leaf order, packed on the device; the float64
     // array carries kLeafMax - 1 padding records (id -1) so a kernel may
@@ -556,7 +533,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
       return rc;
     s->h_nodes = all_nodes;
   }
-  mark("triangle packing");
   int rc = s->nodes.upload(all_nodes);
   if (rc) return rc;
   {  // float32 tree: child refs -> byte offsets (leaves: past the nnodes node records)
@@ -607,7 +583,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     std::vector<DevObjBox> ob;
     dev_obj_boxes(s->obj_boxes, ob);
     if ((rc = s->objbox_dev.upload(ob))) return rc;
-    mark("object bins");
   }
   // everything that depends on the lights (rt_scene_set_lights replaces it)
   s->num_triangles = ntri;
@@ -620,7 +595,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     if (rc) return rc;
     adopt_lights(s.get(), &ls);
   }
-  mark("lights");
   s->max_waves = s->num_cus * 8 * 4;  // 8 blocks of 4 waves per CU at most
   // two kernels per two-class launch: their waves' partial counters side by side
   if ((rc = s->partials.alloc((size_t)2 * s->max_waves * kStatSlots))) return rc;
@@ -629,7 +603,6 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
   if ((rc = s->queue2.alloc(s->queue.n))) return rc;
   HIP_TRY(hipMemset(s->queue2.p, 0, s->queue2.bytes()));
   HIP_TRY(hipDeviceSynchronize());
-  mark("nodes + buffers");
   s->max_depth = maxdepth;
   for (int m = 0; m < d->num_meshes; ++m) {  // the scene keeps the meshes' device arrays (mesh updates)
     std::swap(s->mesh_keep[(size_t)m].verts, d_verts[(size_t)m]);

@@ -322,7 +322,7 @@ class DeviceScene:
 
     def last_lean_kernel(self):
         """Kernels of the last call's two classes: bits 0-1 the lean pixels'
-        (0 none, 1 k_render_lean, 2 k_render_lean1, 3 merged), bits 2-3 the
+        (0 none, 1 k_render_lean, 2 k_render_lean1q, 3 merged), bits 2-3 the
         general pixels' (0 k_render_fast, 1 k_render_gen, 2 k_render_gen1,
         3 merged: k_render_mix1)."""
         k = C.c_int32()
@@ -338,7 +338,8 @@ class DeviceScene:
 
     def last_lean_lanes(self):
         """Lanes per lean pixel of the last two-class call (4 or 16:
-        k_render_lean1q / k_render_mix1; 64: one pixel per wave), 0 if none."""
+        k_render_lean1q / k_render_mix1; 64: k_render_lean, one pixel per
+        wave), 0 if none."""
         k = C.c_int32()
         check(lib().rt_scene_last_lean_kernel(self.h, C.byref(k)))
         return int(k.value) >> 8

@@ -1,7 +1,7 @@
 """Two-class launches of the float32 kernel (rt_render.cpp launch): lean
 pixels — no camera ray can hit the mesh, every light is a distant light whose
 shadow rays provably miss it — render in k_render_lean from a per-launch
-list (k_render_lean1 in one-plane scenes, RT_FLAG_NO_LEAN1 turns it off), the rest in
+list (k_render_lean1q in one-plane scenes, RT_FLAG_NO_LEAN1 turns it off), the rest in
 k_render_gen1 (one-plane scenes, RT_FLAG_NO_GEN1), k_render_gen (several samples per lane through each face
 list; a pixel whose shadow rays need the BVH falls back to the one-sample
 loop) or, where that does not apply, k_render_fast. Scheduling only: frames
@@ -15,6 +15,7 @@ kernel compiled with reflection (they may apply at the camera level only),
 stochastic samplers and progressive passes (step > 1) against the records."""
 import pytest
 
+import cameras
 from rtmi import Antialias, Options, Precision, akGrid, scenes
 from rtmi.abi import (RT_FLAG_BATCH_FALLBACK, RT_FLAG_NO_BATCH, RT_FLAG_NO_BINNING, RT_FLAG_NO_GEN1,
                       RT_FLAG_NO_LEAN1, RT_FLAG_NO_MIX, RT_FLAG_NO_REORDER, RT_FLAG_NO_SPLIT)
@@ -160,7 +161,7 @@ def test_split_full_c3(gpu):
 
 @pytest.mark.parametrize("m", [16, 32])
 def test_lean1_kernel_choice(gpu, m):
-    """k_render_lean1 / k_render_gen1 take the lean / general pixels of
+    """k_render_lean1q / k_render_gen1 take the lean / general pixels of
     one-plane scenes at spp a multiple of 256 (m = 16, 32) with one or two
     distant lights; the general kernels take the others — frames equal
     either way (here and in the FLAG_SETS comparisons above)."""
@@ -211,6 +212,42 @@ def test_lean1_light_sides(gpu, dirs):
         st = ds.render_device(_opts(256, 144, 16, flags), fb)
         assert ds.last_lean_kernel() == kind, (flags, ds.last_lean_kernel())
         assert st == st_ref and torch.equal(fb, ref), (dirs, flags, float((fb - ref).abs().max()))
+
+
+# Launch-plan branches no test above pins (rt_render.cpp Plan): what the
+# call reports, on the one-plane bunny at the size of the tests around it.
+# name: camera (cameras.camera_table), flags -> kernel kinds, lanes per lean
+# pixel, whether lean / batched / ground pixels are reported
+PLAN_ROWS = {
+    # one plane but no batched general kernel: lean1q_loop on its own, the
+    # general list in k_render_fast (gen, gen1, mix and ground off; lean1 on)
+    "no_batch_one_plane": ("std", RT_FLAG_NO_BATCH, 2 | 0 << 2, (4, 16), True, False),
+    # the plan is a two-class launch, but the build finds no lists (the whole
+    # mesh behind the camera plane): the one-kernel launch
+    "no_lists": ("behind", 0, 0, (0,), False, False),
+    # no per-call build at all
+    "no_binning": ("std", RT_FLAG_NO_BINNING, 0, (0,), False, False),
+}
+
+
+@pytest.mark.parametrize("row", list(PLAN_ROWS))
+def test_plan_rows(gpu, row):
+    import torch
+    cam, flags, kind, lanes, lean, batched = PLAN_ROWS[row]
+    s = scenes.mesh_bunny()
+    if cam != "std":
+        s.cameraToWorld, s.fov = cameras.camera_table(s.objects[0].geometry, s.cameraToWorld)[cam]
+    ds = DeviceScene(s)
+    ref = torch.zeros(256 * 144 * 3, dtype=torch.float32, device="cuda")
+    st_ref = ds.render_device(_opts(256, 144, 16, flags | RT_FLAG_NO_LEAN1 | RT_FLAG_NO_GEN1), ref)
+    fb = torch.zeros_like(ref)
+    st = ds.render_device(_opts(256, 144, 16, flags), fb)
+    nlean, ngen = ds.last_split()
+    print(row, ds.last_lean_kernel(), ds.last_lean_lanes(), (nlean, ngen), ds.last_batch(), ds.last_ground())
+    assert ds.last_lean_kernel() == kind and ds.last_lean_lanes() in lanes, (ds.last_lean_kernel(), ds.last_lean_lanes())
+    assert nlean + ngen == 256 * 144 and (nlean > 0) == lean and ngen > 0, (nlean, ngen)
+    assert (ds.last_batch()[0] > 0) == batched and ds.last_ground() == 0, (ds.last_batch(), ds.last_ground())
+    assert st == st_ref and torch.equal(fb, ref), (row, float((fb - ref).abs().max()))
 
 
 @pytest.mark.parametrize("cam_y,bias", [(5.5, 1e-4), (5.5, 1e-7), (5.5, 0.0), (-3.0, 1e-4), (0.5, 1e-4)])
