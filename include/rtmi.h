@@ -247,6 +247,14 @@ typedef struct rt_options {
  * searches alone). The image and Stats are the same, bit for bit
  * (tests/test_gpu_ground.py). */
 #define RT_FLAG_NO_GROUND1 0x10000u
+/* One-plane launches with the one-plane batched kernel: no shortcuts for the
+ * mesh pixels (general pixels with a camera-ray list). By default a sample
+ * slot whose lit shadow origins all lie strictly inside the mesh's box, inset
+ * by the call's margin, skips the mesh's box gate of every light (the gate is
+ * proved false there), and a batch whose samples all hit the mesh, every one
+ * of them inside, is shaded on a straight path without the hit-kind selects.
+ * The image and Stats are the same, bit for bit (tests/test_gpu_mesh1.py). */
+#define RT_FLAG_NO_MESH1 0x20000u
 
 /* Stats (src/renderer/stats.nim:4-13) plus ray counts for Mray/s. */
 typedef struct rt_stats {
@@ -604,6 +612,14 @@ int rt_scene_last_uniform(rt_scene *scene, int32_t *lit, int32_t *sky);
  * one-plane two-class launch with the one-plane batched kernel). Waits for
  * the call. */
 int rt_scene_last_ground(rt_scene *scene, int32_t *ground);
+/* Of the last render call's batches of mesh-pixel samples (64 lanes x the
+ * batch's samples per lane, in the one-plane batched kernel): how many took
+ * the straight path of the description of RT_FLAG_NO_MESH1. 0 with that flag,
+ * for a call the one-plane batched kernel did not serve, and for a call that
+ * counted traversal steps. Valid once the call's Stats have been read (a
+ * render call given `stats`, or rt_scene_last_stats); RT_E_INVALID after a
+ * call that set RT_FLAG_NO_STATS. */
+int rt_scene_last_mesh1(rt_scene *scene, int64_t *straight_batches);
 
 /* ---- ray queries --------------------------------------------------------
  * trace (renderer.nim:47-67) itself — "what does this ray hit, and where" —

@@ -532,5 +532,61 @@ __host__ __device__ inline int uniform_class(const UniformCam& u, int x, int y) 
   return lo > (double)1e-6f ? kUniLit : kUniMixed;
 }
 
+// ---- mesh pixels of gen1_loop (rt_fast.h gen1_batch): the inset box -------
+//
+// A shadow ray that leaves a hit on the mesh starts inside the mesh's box, and
+// the gate (rt_fast.h mesh_gate: "a ray starting inside the box misses")
+// answers false. The kernel proves that ahead of the gate with one test of the
+// ray's origin against a box inset by a margin, the same for every light.
+//
+// lo, hi: the mesh object's float32 FObj.lo / FObj.hi. In float64,
+//   m = 2^-12 max(|lo|_inf, |hi|_inf),
+//   in_lo = nextafter(float(lo + m), +inf), in_hi = nextafter(float(hi - m), -inf),
+// so a float strictly between in_lo and in_hi on an axis is more than m away
+// from both of the box's planes there (the two roundings to float are
+// covered by the step outwards of the true value).
+//
+// Lemma 1. ro strictly inside the inset box on all three axes, ni any floats
+// with 1e-6 <= |ni| <= 1e20 (slab_ray's reciprocals, whatever v_rcp's last
+// bit): mesh_gate is false. On an axis, with oi = fl(ro ni):
+//   a = fl(lo ni - oi), b = fl(hi ni - oi)   (one rounding each: FMAs)
+//   lo ni - oi = (lo - ro) ni + (ro ni - oi), |ro ni - oi| <= 2^-24 |ro| |ni|,
+//   |(lo - ro) ni| > m |ni| >= 2^-12 |ro| |ni|   (|ro| < max(|lo|, |hi|)),
+// so the exact lo ni - oi has the sign of (lo - ro) ni and the exact hi ni - oi
+// the opposite one, both at least m |ni| (1 - 2^-12) >= 0.99e-31 in magnitude
+// (m >= 1e-25): normal numbers, whose rounding keeps the sign, and at most
+// 2e15 x 1e20 x 2: finite (|coordinates| <= 1e15). A product ro ni in the
+// denormal range errs by at most 2^-149, far below m |ni|. So fminf(a, b) < 0
+// on every axis, gmin < 0, and the gate's "gmin >= 0" fails.
+//
+// The call's condition (else the box is empty: lo = +inf, hi = -inf, no value
+// is strictly between): every light's |v|_inf <= 1e6 (so |ni| >= 0.99e-6 on
+// an unclamped component; a clamped one has |ni| = 1e20 within an ulp),
+// m >= 1e-25, |coordinates| <= 1e15, in_lo < in_hi on all three axes.
+struct InsetBox {
+  float lo[3], hi[3];
+};
+// light_v: every light's FLight::v (3 floats each)
+__host__ __device__ inline void inset_box(const float* lo, const float* hi, const float* light_v, int nl, InsetBox& b) {
+  double amax = 0.0;
+  for (int k = 0; k < 3; ++k) amax = dmax(amax, dmax(fabs((double)lo[k]), fabs((double)hi[k])));
+  const double m = amax * (1.0 / 4096.0);
+  bool ok = m >= 1e-25 && amax <= 1e15;  // (false for a NaN)
+  for (int l = 0; l < 3 * nl; ++l) ok = ok && fabsf(light_v[l]) <= 1e6f;
+  for (int k = 0; k < 3; ++k) {
+    b.lo[k] = nextafterf((float)((double)lo[k] + m), INFINITY);
+    b.hi[k] = nextafterf((float)((double)hi[k] - m), -INFINITY);
+    ok = ok && b.lo[k] < b.hi[k];
+  }
+  if (!ok)
+    for (int k = 0; k < 3; ++k) {
+      b.lo[k] = INFINITY;
+      b.hi[k] = -INFINITY;
+    }
+}
+// (The kernel's test of a shadow origin against the box, compares alone, is
+// rt_common.h inset_inside: the float32 kernels' unit does not include this
+// file, whose float64 geometry is compiled without FMA contraction.)
+
 }  // namespace bg
 }  // namespace rtmi

@@ -35,7 +35,9 @@ enum : int32_t { LIGHT_DISTANT = 0, LIGHT_POINT = 1 };
 // DevObject.xf: what world_to_object is (host-classified, float32 fast paths)
 enum : int32_t { XF_IDENTITY = 0, XF_TRANSLATE = 1, XF_GENERAL = 2 };
 // RenderParams.flags bits
-enum : int32_t { RT_DEV_FLAG_COUNT = 0x2, RT_DEV_FLAG_FALLBACK = 0x40, RT_DEV_FLAG_NO_OBJ_BATCH = 0x1000 };
+enum : int32_t {
+  RT_DEV_FLAG_COUNT = 0x2, RT_DEV_FLAG_FALLBACK = 0x40, RT_DEV_FLAG_NO_OBJ_BATCH = 0x1000, RT_DEV_FLAG_NO_MESH1 = 0x20000
+};
 
 constexpr int kMaxBvhDepth = 60;      // stack fits one 64-lane VGPR
 constexpr int kLeafMax = 4;           // triangles per BVH leaf (arrays padded by kLeafMax-1)
@@ -280,6 +282,17 @@ enum : int { kUniMixed = 0, kUniLit = 1, kUniSky = 2 };
 // other launch's general list holds plain group indices.
 constexpr int32_t kGenGroundBit = 1 << kLeanClsShift;
 
+// gen1_batch's test of a shadow origin in the mesh's frame against the
+// call's inset box (FastParams.in_lo / in_hi; rt_bins_geom.h inset_box and
+// lemma 1): strictly inside on all three axes. False for a NaN and for the
+// empty box.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool inset_inside(float lx, float ly, float lz, float hx, float hy, float hz, float x, float y, float z) {
+  return x > lx && x < hx && y > ly && y < hy && z > lz && z < hz;
+}
+
 struct LTri;
 struct FastParams {
   const FObj* objs;
@@ -357,6 +370,11 @@ struct FastParams {
   // its faces' records straight from the cell's range — one load per step
   // instead of the entry, then the record it names; nullptr: via grid_ent
   const LTri* grid_rec;
+  // gen1_loop launches: the mesh's box inset by the call's margin
+  // (rt_bins_geom.h inset_box, lemma 1) — a shadow origin strictly inside it,
+  // in the mesh's frame, fails the mesh gate for every light; empty (+inf,
+  // -inf) where the call's condition fails or with RT_FLAG_NO_MESH1
+  float in_lo[3], in_hi[3];
 };
 // A face's shadow-ray test for one distant light (fixed direction d, mesh
 // object space), prepared in float64 by the host (rtmi.cpp make_ltri): with

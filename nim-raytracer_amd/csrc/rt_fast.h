@@ -2161,7 +2161,11 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
     for (int k = 0; k < S; ++k) {
       ro[k] = f3(o.x + mob.t[0], o.y + mob.t[1], o.z + mob.t[2]);
       rd[k] = d[k];
+#ifdef RTMI_DIAG_MESH1_CEIL  // timing only (wrong images): no camera gate
+      const bool part = true;
+#else
       const bool part = mesh_gate(mob, slab_ray(ro[k], rd[k]));
+#endif
       tc[k] = part ? th[k] : -1.0f;
       key0[k] = part ? tkey(th[k], 0u) : 0ull;
       key[k] = key0[k];
@@ -2215,22 +2219,102 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
                __builtin_fmaf(d[k].z, th[k], o.z));
   }
   const int nbase = at(p->objx, mesh).normal_base;
+  // mesh pixels (off with RT_FLAG_NO_MESH1). all: every sample of the batch
+  // is lit by a hit on the mesh, so the selects below are wave-uniformly
+  // decided — N the face normal, the albedo the mesh's, no background.
+  const bool m1 = (p->flags & RT_DEV_FLAG_NO_MESH1) == 0;
+  bool all = m1;
+  {
+    const unsigned long long full = bal(true);
 #pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const bool lt = lane_in(litm[k]);
-    F3 n = f3(0.0f, 1.0f, 0.0f);
-    if (anymesh != 0ull) {  // every lane loads (face 0 for the others): no exec-mask branch
-      const bool mi = lt && hm[k];
-      const float* fn = p->normals + 3 * (size_t)(nbase + (mi ? htri[k] : 0));
-      n = f3(mi ? fn[0] : n.x, mi ? fn[1] : n.y, mi ? fn[2] : n.z);
+    for (int k = 0; k < S; ++k) all = all && (bal(hm[k]) & litm[k]) == full;
+  }
+#ifdef RTMI_DIAG_MESH1_CEIL  // timing only (wrong images): every pixel with a list takes the straight path
+  all = (pinfo & kPixCount) != 0u;
+#endif
+  if (all) {
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+#ifdef RTMI_DIAG_MESH1_CEIL
+      const float* fn = p->normals + 3 * (size_t)(nbase + max(htri[k], 0));
+#else
+      const float* fn = p->normals + 3 * (size_t)(nbase + htri[k]);
+#endif
+      N[k] = f3(fn[0], fn[1], fn[2]);
     }
-    N[k] = f3(lt ? n.x : 0.0f, lt ? n.y : 0.0f, lt ? n.z : 0.0f);
+  } else {
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const bool lt = lane_in(litm[k]);
+      F3 n = f3(0.0f, 1.0f, 0.0f);
+      if (anymesh != 0ull) {  // every lane loads (face 0 for the others): no exec-mask branch
+        const bool mi = lt && hm[k];
+        const float* fn = p->normals + 3 * (size_t)(nbase + (mi ? htri[k] : 0));
+        n = f3(mi ? fn[0] : n.x, mi ? fn[1] : n.y, mi ? fn[2] : n.z);
+      }
+      N[k] = f3(lt ? n.x : 0.0f, lt ? n.y : 0.0f, lt ? n.z : 0.0f);
+    }
   }
   const float bias = p->bias;
 #pragma unroll
   for (int k = 0; k < S; ++k)
     so[k] = f3(__builtin_fmaf(N[k].x, bias, so[k].x), __builtin_fmaf(N[k].y, bias, so[k].y),
                __builtin_fmaf(N[k].z, bias, so[k].z));
+  // gate: the sample slots whose shadow rays evaluate the mesh gate. A slot
+  // whose lit lanes' origins all lie strictly inside the call's inset box
+  // (in the mesh's frame, as shadow_mesh forms them) does not: the gate is
+  // false there for every light (rt_bins_geom.h lemma 1).
+  unsigned gate = (1u << S) - 1u;
+  if (m1) {
+    const float lx = p->in_lo[0], ly = p->in_lo[1], lz = p->in_lo[2];
+    const float hx = p->in_hi[0], hy = p->in_hi[1], hz = p->in_hi[2];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const bool in = inset_inside(lx, ly, lz, hx, hy, hz, so[k].x + mob.t[0], so[k].y + mob.t[1], so[k].z + mob.t[2]);
+      if ((litm[k] & ~bal(in)) == 0ull) gate &= ~(1u << k);
+    }
+  }
+#ifdef RTMI_DIAG_MESH1_CEIL  // timing only: no shadow gate for a pixel with a list
+  if (all) gate = 0u;
+#endif
+  if (all && gate == 0u) {
+    // the straight path: every sample a mesh hit whose shadow rays cannot
+    // meet the mesh. What is left per light is the plane's shadow test and
+    // the irradiance term — the operations of the code below, operand for
+    // operand, with litm full, hm true and every mesh gate false.
+    F3 E[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) E[k] = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int li = 0; li < NL; ++li) {
+      p = params();
+      const FLight L = at(p->lights, li);
+      const F3 sd = f3(-L.v[0], -L.v[1], -L.v[2]);
+      const float mulp = fabsf(sd.y) > 1e-6f ? rcp(sd.y) : __builtin_nanf("");
+#pragma unroll
+      for (int k = 0; k < S; ++k) {
+        const float tpl = -(so[k].y + pty) * mulp;
+        const bool c = tpl >= 0.0f && tpl < finf();  // ts = +inf: the plane occludes
+        hitl += c ? 1u : 0u;
+        irr_add(E[k], L.ci, c ? 0.0f : fmaxf(dot3(N[k], sd), 0.0f));
+      }
+    }
+    p = params();
+    const RT_CONST FObjX& mx = at(p->objx, mesh);
+    const F3 am = f3(mx.albedo_pi[0], mx.albedo_pi[1], mx.albedo_pi[2]);
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const F3 a = mul3(am, E[k]);
+      acc_add3(acc, a.x, a.y, a.z);
+    }
+    wi.v[STAT_PRIMARY] += (unsigned)(64 * S);
+    wi.v[STAT_SHADOW] += (unsigned)(NL * 64 * S);
+    wi.v[STAT_HITS] += wave_sum(hitl);
+#if !defined(RTMI_DIAG_GEN_COUNT) && !defined(RTMI_DIAG_LANES)
+    wi.v[STAT_LANE_TRIS] += 1u;  // rt_scene_last_mesh1 (a slot only counting launches write otherwise)
+#endif
+    return true;
+  }
   // one shadow ray per distant light and lit sample
   F3 E[S];
 #pragma unroll
@@ -2267,7 +2351,7 @@ __device__ __forceinline__ bool gen1_batch(KP p, const GroupPix& gp, int pu, int
         for (int k = 0; k < S; ++k) {
           ro[k] = f3(so[k].x + mob.t[0], so[k].y + mob.t[1], so[k].z + mob.t[2]);
           rd[k] = sd;
-          pm[k] = bal(lane_in(litm[k]) && mesh_gate(mob, slab_ray(ro[k], rd[k])));
+          pm[k] = ((gate >> k) & 1u) != 0u ? bal(lane_in(litm[k]) && mesh_gate(mob, slab_ray(ro[k], rd[k]))) : 0ull;
           anyp |= pm[k];
         }
         if (anyp == 0ull) return true;
@@ -3617,6 +3701,8 @@ __device__ __forceinline__ void gen1_loop(KP p, LdsF* ls, Stats32& ws, unsigned 
       ws.v[STAT_HITS] += wi.v[STAT_HITS];
 #if defined(RTMI_DIAG_GEN_COUNT) || defined(RTMI_DIAG_LANES)
       for (int q = STAT_NODE_FETCH; q <= STAT_LANE_TRIS; ++q) ws.v[q] += wi.v[q];
+#else
+      ws.v[STAT_LANE_TRIS] += wi.v[STAT_LANE_TRIS];  // gen1_batch's straight-path batches
 #endif
     } else {  // some shadow ray needs the BVH: the whole pixel by the one-sample loop
       acc.v = f3(0.0f, 0.0f, 0.0f);

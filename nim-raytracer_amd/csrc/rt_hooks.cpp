@@ -132,6 +132,38 @@ extern "C" int rtmi_test_uniform(const double* c2w, double fov, int32_t w, int32
   return RT_OK;
 }
 
+// Test hook for the mesh pixels' inset box (tests/test_mesh1_cpu.py; no
+// device). box6: bg::inset_box of the float32 box lo / hi and the nl lights'
+// FLight.v (in_lo, in_hi). Per case i of n, with the origin ro[3 i ..] in the
+// mesh's frame and the reciprocals ni[3 i ..] given (so that the test can
+// move them by an ulp, as v_rcp may): inside[i] = the kernel's inset_inside,
+// gate[i] = rt_fast.h mesh_gate restated in float32 with fmaf where the
+// kernel has an FMA (this unit is compiled without contraction).
+extern "C" int rtmi_test_mesh1(const float* lo, const float* hi, const float* light_v, int32_t nl, float* box6,
+                               int64_t n, const float* ro, const float* ni, uint8_t* inside, uint8_t* gate) {
+  if (!lo || !hi || nl < 0 || (nl > 0 && !light_v) || !box6 || n < 0 || (n > 0 && (!ro || !ni || !inside || !gate)))
+    return fail(RT_E_INVALID, "bad argument");
+  bg::InsetBox b;
+  bg::inset_box(lo, hi, light_v, nl, b);
+  std::copy(b.lo, b.lo + 3, box6);
+  std::copy(b.hi, b.hi + 3, box6 + 3);
+  for (int64_t i = 0; i < n; ++i) {
+    const float* o = ro + 3 * i;
+    const float* r = ni + 3 * i;
+    inside[i] = inset_inside(b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2], o[0], o[1], o[2]) ? 1 : 0;
+    float a[3], c[3];
+    for (int k = 0; k < 3; ++k) {
+      const float oi = o[k] * r[k];
+      a[k] = fmaf(lo[k], r[k], -oi);
+      c[k] = fmaf(hi[k], r[k], -oi);
+    }
+    const float gmin = fmaxf(fmaxf(fminf(a[0], c[0]), fminf(a[1], c[1])), fminf(a[2], c[2]));
+    const float gmax = fminf(fminf(fmaxf(a[0], c[0]), fmaxf(a[1], c[1])), fmaxf(a[2], c[2])) * 1.00000024f;
+    gate[i] = gmin <= gmax && gmin >= 0.0f ? 1 : 0;
+  }
+  return RT_OK;
+}
+
 // The one-plane kernel's cx (m per pixel column), cy (m per pixel row) and N
 // (m x m per pixel: pixels row by row, then the sample row j, then the sample
 // column i) for every sample of the same rectangle: the expressions listed

@@ -744,6 +744,16 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   *split = false;
   *zeroed = false;
   plan_kernels(s, o, mp, p, pl);
+  s->mesh1 = pl.gen1 && !(o->flags & RT_FLAG_NO_MESH1);
+  if (s->mesh1) {  // gen1_loop's inset box (rt_bins_geom.h inset_box): the kernel's own float32 values
+    const FObj& mo = s->h_fo[(size_t)s->shadow_mesh];
+    bg::InsetBox ib;
+    bg::inset_box(mo.lo, mo.hi, s->h_light_v.data(), s->nlight, ib);
+    for (int k = 0; k < 3; ++k) {
+      p.in_lo[k] = ib.lo[k];
+      p.in_hi[k] = ib.hi[k];
+    }
+  }
   if (!pl.build) return RT_OK;
   // this call's camera-dependent data (nothing of it is kept from earlier calls)
   int rc;
@@ -1078,6 +1088,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
   s->fr.listed = false;
   s->fr.uniform = false;
   s->fr.ground = false;
+  s->mesh1 = false;
   s->pending_reduce = 0;
   s->last_lean = 0;
   s->last_lean_kind = 0;
@@ -1095,6 +1106,7 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
     bool split = false, zeroed = false;
     int rc = fill_fast(s, o, mp, d_out, p, pl, &measuring, st, &split, zero, nzero, &zeroed);
     if (rc) return rc;
+    s->mesh1 = s->mesh1 && split;  // (without lists the call is a one-kernel launch)
     if (!zeroed && (rc = clear())) return rc;
     if (o->flags & RT_FLAG_TIMING) HIP_TRY(hipEventRecord(s->tev[1], st));
     s->last_general = p.ngroups;
@@ -1143,6 +1155,7 @@ int read_stats(rt_scene* s, hipStream_t st, rt_stats* out) {
   out->num_shadow_rays = h[STAT_SHADOW];
   out->num_reflection_rays = h[STAT_REFL];
   s->last_fallback = (int64_t)h[STAT_GEN_FALLBACK];
+  s->last_straight = (int64_t)h[STAT_LANE_TRIS];
   return RT_OK;
 }
 
@@ -1350,6 +1363,15 @@ extern "C" int rt_scene_last_ground(rt_scene* s, int32_t* ground) {
   return RT_OK;
 }
 
+extern "C" int rt_scene_last_mesh1(rt_scene* s, int64_t* straight_batches) {
+  if (!s || !straight_batches) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->stats_kept) return fail(RT_E_INVALID, "the last render call set RT_FLAG_NO_STATS");
+  // the slot is the straight-path count only where gen1_loop ran uninstrumented
+  *straight_batches = s->mesh1 ? s->last_straight : 0;
+  return RT_OK;
+}
+
 extern "C" int rt_scene_last_lean_kernel(rt_scene* s, int32_t* kind) {
   if (!s || !kind) return fail(RT_E_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
@@ -1385,6 +1407,8 @@ extern "C" int rt_scene_last_counters(rt_scene* s, rt_traversal_counters* out) {
   out->wave_node_fetches = h[STAT_NODE_FETCH];
   out->wave_tri_fetches = h[STAT_TRI_FETCH];
   out->lane_node_visits = h[STAT_LANE_NODES];
-  out->lane_tri_tests = h[STAT_LANE_TRIS];
+  // (an uninstrumented gen1_loop launch keeps its straight-path batches in
+  // this slot, rt_scene_last_mesh1: no traversal counter)
+  out->lane_tri_tests = s->mesh1 ? 0 : h[STAT_LANE_TRIS];
   return RT_OK;
 }

@@ -107,6 +107,12 @@ struct rt_scene {
   // host copies of what the per-call uniform-pixel condition reads (uniform_cam):
   // every object's FObj.t[1], every light's FLight.v[1]
   std::vector<float> h_obj_ty, h_light_vy;
+  // every light's FLight.v (3 floats each): the inset box's condition (rt_bins_geom.h inset_box)
+  std::vector<float> h_light_v;
+  // rt_scene_last_mesh1: the last call's general list went to gen1_loop
+  // without RT_FLAG_NO_MESH1, and its straight-path batches (read_stats)
+  bool mesh1 = false;
+  int64_t last_straight = 0;
   int32_t last_lean_kind = 0;                // rt_scene_last_lean_kernel
   bool stats_kept = true;                    // the last call kept its Stats (no RT_FLAG_NO_STATS)
   // per-wave Stats rows of the last call not yet reduced into acc(): a call
@@ -318,7 +324,7 @@ void parallel_for(int64_t n, Fn fn) {
 struct LightState {
   std::vector<rt_light_desc> desc;
   int32_t has_point_light = 0;
-  std::vector<float> h_light_vy;
+  std::vector<float> h_light_vy, h_light_v;
   DevBuf<FLight> f32_lights;
   DevBuf<DevLight<double>> f64_lights;
   DevBuf<LightGrid> grids;

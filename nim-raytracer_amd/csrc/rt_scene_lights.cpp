@@ -296,7 +296,10 @@ int build_lights(rt_scene* s, const rt_light_desc* lights, int32_t nl, bool devi
     std::vector<DevLight<double>> dl;
     fill_fast_lights(lights, nl, fl);
     fill_lights<double>(lights, nl, dl);
-    for (const FLight& q : fl) L->h_light_vy.push_back(q.v[1]);
+    for (const FLight& q : fl) {
+      L->h_light_vy.push_back(q.v[1]);
+      L->h_light_v.insert(L->h_light_v.end(), q.v, q.v + 3);
+    }
     if ((rc = L->f32_lights.upload(fl)) || (rc = L->f64_lights.upload(dl))) return rc;
   }
   const int nobj = (int)s->obj_meta.size();
@@ -368,6 +371,7 @@ void adopt_lights(rt_scene* s, LightState* L) {
   s->has_point_light = L->has_point_light;
   s->f32_subset = (s->f32_subset & ~(unsigned)SUB_POINT) | (s->has_point_light ? (unsigned)SUB_POINT : 0u);
   std::swap(s->h_light_vy, L->h_light_vy);
+  std::swap(s->h_light_v, L->h_light_v);
   std::swap(s->f32.lights, L->f32_lights);
   std::swap(s->f64.lights, L->f64_lights);
   std::swap(s->grids, L->grids);

@@ -35,6 +35,7 @@ RT_FLAG_COMPACT = 0x2000
 RT_FLAG_F64_PER_LANE = 0x4000
 RT_FLAG_NO_UNIFORM = 0x8000
 RT_FLAG_NO_GROUND1 = 0x10000
+RT_FLAG_NO_MESH1 = 0x20000
 RT_QUERY_ANY_HIT = 0x1
 RT_QUERY_SORT = 0x2
 RT_BVH_SAH = 0
@@ -204,6 +205,7 @@ SIGNATURES = {
     "rt_scene_last_batch": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rt_scene_last_uniform": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_scene_last_ground": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "rt_scene_last_mesh1": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rt_mat4_inverse": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_load_geom": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "rt_ppm_encode_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

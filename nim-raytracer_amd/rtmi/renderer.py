@@ -320,6 +320,14 @@ class DeviceScene:
         check(lib().rt_scene_last_ground(self.h, C.byref(a)))
         return int(a.value)
 
+    def last_mesh1(self):
+        """The last call's batches of mesh-pixel samples that took the
+        one-plane batched kernel's straight path (0 when none could: see
+        RT_FLAG_NO_MESH1). Valid once the call's Stats have been read."""
+        a = C.c_int64()
+        check(lib().rt_scene_last_mesh1(self.h, C.byref(a)))
+        return int(a.value)
+
     def last_lean_kernel(self):
         """Kernels of the last call's two classes: bits 0-1 the lean pixels'
         (0 none, 1 k_render_lean, 2 k_render_lean1q, 3 merged), bits 2-3 the
