@@ -709,7 +709,8 @@ int rt_pick_pixels(rt_scene *scene, const rt_options *opts, int64_t n,
  * thin-lens camera with its own samples, a light probe or cube map at a
  * point, radiance baked at surface points, a preview of what a mirror shows.
  * The caller forms the rays; the library answers with the reference's colour,
- * float64 operation for operation (there is no float32 mode).
+ * float64 operation for operation (the float32 mode's colours:
+ * rt_shade_rays_f32 below).
  *
  * Ray i is initRay(orig_i, dir_i) (geom.nim:41-48) with depth 1; dir is taken
  * as given, NOT normalised, as in rt_trace_rays. Its colour is
@@ -758,6 +759,61 @@ int rt_shade_rays_device(rt_scene *scene, const rt_options *opts, int64_t n,
 int rt_shade_rays(rt_scene *scene, const rt_options *opts, int64_t n,
                   const double *orig, const double *dir, int32_t group,
                   uint32_t flags, double *rgb, float *rgb32, rt_stats *out);
+
+/* ---- float32 radiance queries --------------------------------------------
+ * rt_shade_rays in the float32 mode's arithmetic, for callers that form many
+ * rays per frame (a custom camera at 256 samples per pixel): float32 rays in
+ * (24 bytes per ray), float32 colours out, the BVH path of the RT_FP32 render.
+ *
+ * Ray i is (orig[3i..], dir[3i..]), float32; dir is taken as given, NOT
+ * normalised. Its colour is what the RT_FP32 render computes for a camera
+ * sample with that ray: shade(ray, trace(ray)) in the arithmetic of the
+ * float32 render kernel (shadow rays to distant lights keep their light-grid
+ * searches, which depend on the lights and the geometry only). The scene's
+ * camera is not read. Accuracy is the float32 mode's, stated
+ * for bias >= 1e-4: with a bias near 1e-8 a float32 shadow ray starts inside
+ * the rounding error of its own hit point and surfaces shadow themselves, as
+ * INTEGRATION.md warns for RT_FP32 renders.
+ *  - opts: bias, max_ray_depth, precision and flags are read. precision must
+ *    be RT_FP32 (RT_FP64 is RT_E_INVALID: rt_shade_rays is the float64
+ *    query). Of opts->flags only RT_FLAG_NO_BINNING is honoured — shadow rays
+ *    then search the BVH instead of the light-grid cells, with the same bytes
+ *    out — and every other bit is ignored. With reflective materials
+ *    max_ray_depth above 7 is RT_E_UNSUPPORTED, as for a render.
+ *  - group >= 1 and n % group == 0, else RT_E_INVALID; rgb holds n / group
+ *    colours of three floats. group == 1: the ray's colour as computed.
+ *    group > 1: starting from +0, the float32 sum of the group's colours in
+ *    index order, times (float)(1.0 / (double)group) — the render's inv_len.
+ *  - A degenerate ray — a non-finite component or an all-zero direction —
+ *    has the colour (+0, +0, +0) and adds nothing to the Stats; it
+ *    contributes +0 to its group's sum, and the group still divides by
+ *    `group`. A finite ray of any magnitude never faults; where float32
+ *    arithmetic overflows, its colour is unspecified and may be non-finite.
+ *  - out (may be NULL) receives all five fields: num_primary_rays is the
+ *    number of rays that are not degenerate, the other four are what the
+ *    float32 kernels count. A _device call with out == NULL only enqueues
+ *    work on hip_stream; with out it waits.
+ *  - flags: RT_QUERY_SORT shades the rays in rt_trace_rays' coherence order
+ *    (the keys are formed from the float values). RT_QUERY_ANY_HIT and unknown
+ *    bits are RT_E_INVALID.
+ *  - The colour and the Stats contribution of ray i depend on ray i, the
+ *    scene and opts only: not on n, the ray's index, its neighbours in the
+ *    batch, RT_QUERY_SORT, RT_FLAG_NO_BINNING, or the host versus the device
+ *    form. The same holds byte for byte for group outputs.
+ * Locking, ordering and edge cases are rt_shade_rays's: n == 0 is RT_OK with
+ * zero Stats (group is still checked); n < 0 and null required pointers are
+ * RT_E_INVALID; n >= 2^31 is RT_E_UNSUPPORTED; everything rt_scene_last_*
+ * reports stays the last render call's. */
+
+/* Device form: d_orig / d_dir (n*3 floats) and d_rgb (n/group*3 floats) are
+ * device memory. */
+int rt_shade_rays_f32_device(rt_scene *scene, const rt_options *opts, int64_t n,
+                             const float *d_orig, const float *d_dir, int32_t group,
+                             uint32_t flags, float *d_rgb, void *hip_stream, rt_stats *out);
+/* Host form: the same arrays in caller memory; returns with the answers. */
+int rt_shade_rays_f32(rt_scene *scene, const rt_options *opts, int64_t n,
+                      const float *orig, const float *dir, int32_t group,
+                      uint32_t flags, float *rgb, rt_stats *out);
 
 /* ---- helpers ----------------------------------------------------------- */
 

@@ -396,6 +396,16 @@ struct alignas(16) LTri {
   int32_t pad[3];
 };
 static_assert(sizeof(LTri) == 64, "LTri must be 64 bytes (one scalar load, TriFast-sized offsets)");
+// One batch of a float32 radiance query (rt_shade_rays_f32*, k_shade_rays_f32;
+// all pointers device memory): the kernel's second argument, after the
+// FastParams that params() reads from kernarg offset 0.
+struct Shade32Params {
+  const float* orig;      // n * 3
+  const float* dir;       // n * 3, as given
+  const uint32_t* order;  // RT_QUERY_SORT: slot k shades ray order[k]; nullptr: ray k
+  float* rgb;             // n * 3: ray i's colour at rgb[3 i] (group > 1: a temporary k_shade_reduce32 sums)
+  long long n;
+};
 // reflection queue of a k_render_wave wave: up to 63 rays left over plus a
 // pass's 64 new ones; fields ro xyz, rd xyz, weight, dst * 16 + depth
 constexpr int kReflQueue = 128, kReflFields = 9;
@@ -414,8 +424,9 @@ enum : unsigned {
 };
 // the float32 kernel families of a feature subset: every subset has the
 // render kernel, some the lean / batched general pair or the
-// reflection-compacting kernel (rt_kernels_f32_part.hip)
-enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3 };
+// reflection-compacting kernel (rt_kernels_f32_part.hip); the non-stochastic
+// subsets also have the float32 radiance-query kernel (rt_fast_shade.h)
+enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3, K32_SHADE = 4 };
 // float32 kernel work queue: 64 head words, 128 B apart, zeroed per launch
 constexpr int kQueueShards = 64, kQueueStride = 32;
 // object-binned batches (k_render_fast, analytic scenes with distant lights,
@@ -454,6 +465,14 @@ int rtmi_launch_mix1_f32(const rtmi::FastParams* p, int nl, int lp, int blocks, 
 int rtmi_mix1_f32_blocks_per_cu(int nl, int lp);
 int rtmi_launch_gen_f32(const rtmi::FastParams* p, unsigned subset, int blocks, size_t shmem, void* stream);
 int rtmi_gen_f32_blocks_per_cu(unsigned subset, size_t shmem);
+// k_shade_rays_f32 of a non-stochastic feature subset (rt_fast_shade.h), and
+// its group sums: ngroups outputs, each the ordered float32 sum of `group`
+// ray colours times inv_len
+int rtmi_launch_shade_f32(const rtmi::FastParams* p, const rtmi::Shade32Params* q, unsigned subset, int blocks,
+                          void* stream);
+int rtmi_shade_f32_blocks_per_cu(unsigned subset);
+int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int group, float inv_len, float* rgb,
+                               void* stream);
 int rtmi_launch_ppm_encode(const float* fb, long long n, int bits, int srgb, void* out, void* stream);
 int rtmi_launch_rgba_encode(const float* fb, long long npix, unsigned int alpha, void* out, void* stream);
 // Sets this thread's rt_last_error() text; returns code (rtmi.cpp).

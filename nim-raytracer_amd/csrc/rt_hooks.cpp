@@ -64,6 +64,15 @@ extern "C" int rtmi_test_f32_subset(rt_scene* s, const rt_options* o) {
   return (int)f32_subset(s, o);
 }
 
+// The specialisation of k_shade_rays_f32 a float32 radiance query
+// (rt_shade_rays_f32*) launches on this scene: the scene's SUB_* bits without
+// stochastic sampling, as shade32_device reads them.
+extern "C" int rtmi_test_shade32_subset(rt_scene* s) {
+  if (!s) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  return (int)(s->f32_subset & ~(unsigned)SUB_STOCHASTIC & 63u);
+}
+
 // Test hook: the LTri record (rt_common.h) of triangle v9 (v0, v1, v2 as 9
 // doubles, mesh object space) for the shadow direction d (float64), as
 // rt_scene_create builds it; out: 16 words.

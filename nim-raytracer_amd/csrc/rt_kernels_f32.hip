@@ -65,6 +65,27 @@ __global__ __launch_bounds__(256) void k_sec_add(float* __restrict__ fb, const l
   }
 }
 
+// After k_shade_rays_f32 with group > 1: the render's pixel sum over each run
+// of `group` ray colours — from +0, added in index order in float32 (one
+// thread per output walks its run, never a tree, so the sum does not depend
+// on how the batch was split), then one multiplication by inv_len. The adds
+// and the multiply stay apart (nothing here can contract).
+__global__ __launch_bounds__(256) void k_shade_reduce32(const float* __restrict__ ray_rgb, long long ngroups, int group,
+                                                        float inv_len, float* __restrict__ rgb) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ngroups) return;
+  const float* c = ray_rgb + 3 * k * group;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  for (int j = 0; j < group; ++j) {
+    x = x + c[3 * j];
+    y = y + c[3 * j + 1];
+    z = z + c[3 * j + 2];
+  }
+  rgb[3 * k] = x * inv_len;
+  rgb[3 * k + 1] = y * inv_len;
+  rgb[3 * k + 2] = z * inv_len;
+}
+
 // the instrumented (RT_FLAG_COUNT_TRAVERSAL) kernel: all features
 template __global__ void fast::k_render_fast<true, fast::F_ALL>(const FastParams);
 // lean pixels of one-plane scenes (rt_render.cpp lean1_ok), one or two lights, 4 or 16 lanes per pixel
@@ -176,6 +197,30 @@ extern "C" int rtmi_launch_gen_f32(const rtmi::FastParams* p, unsigned subset, i
 // Resident blocks per CU of the batched general kernel; 0: none for the subset.
 extern "C" int rtmi_gen_f32_blocks_per_cu(unsigned subset, size_t shmem) {
   return blocks_per_cu(subset_kernel(rtmi::K32_GEN, subset), 0, shmem);
+}
+
+// The float32 radiance-query kernel of a non-stochastic feature subset
+// (rt_fast_shade.h): its arguments are the FastParams, then the batch.
+extern "C" int rtmi_launch_shade_f32(const rtmi::FastParams* p, const rtmi::Shade32Params* q, unsigned subset,
+                                     int blocks, void* stream) {
+  const void* fn = subset < 64u ? subset_kernel(rtmi::K32_SHADE, subset) : nullptr;
+  if (!fn) return (int)hipErrorInvalidDeviceFunction;
+  void* args[] = {const_cast<rtmi::FastParams*>(p), const_cast<rtmi::Shade32Params*>(q)};
+  (void)hipLaunchKernel(fn, dim3(blocks), dim3(256), args, 0, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
+// Resident blocks per CU of the radiance-query kernel; 0: none for the subset.
+extern "C" int rtmi_shade_f32_blocks_per_cu(unsigned subset) {
+  return blocks_per_cu(subset < 64u ? subset_kernel(rtmi::K32_SHADE, subset) : nullptr, 0, 0);
+}
+
+extern "C" int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int group, float inv_len,
+                                          float* rgb, void* stream) {
+  const unsigned blocks = (unsigned)((ngroups + 255) / 256);
+  hipLaunchKernelGGL(rtmi::k_shade_reduce32, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ray_rgb, ngroups, group,
+                     inv_len, rgb);
+  return (int)hipGetLastError();
 }
 
 // The lean-pixel kernel of a feature subset (two-class launches).

@@ -7,6 +7,7 @@
 // without the sphere / box / rotation / point-light / reflection code paths
 // (fewer branches, fewer SALU, 66 instead of 72+ VGPRs).
 #include "rt_fast.h"
+#include "rt_fast_shade.h"
 
 #ifndef RTMI_PART
 #error "compile with -DRTMI_PART=<0..15>"
@@ -29,6 +30,9 @@ constexpr unsigned subset_mask(unsigned i) {
 constexpr bool has_lean(unsigned i) { return (i & 4u) && !(i & 32u) && !(i & 16u); }
 // the reflection-compacting kernel exists for the reflective subsets
 constexpr bool has_wave(unsigned i) { return (i & 32u) != 0u; }
+// the float32 radiance-query kernel reads its rays from memory: it exists for
+// the subsets without stochastic sampling
+constexpr bool has_shade(unsigned i) { return (i & 64u) == 0u; }
 
 // The host address of kernel (family, subset I), null where the family has
 // none for the subset. Taking an address instantiates the kernel.
@@ -46,6 +50,9 @@ const void* kernel_of(int family) {
       break;
     case rtmi::K32_WAVE:
       if constexpr (has_wave(I)) return (const void*)f::k_render_wave<F>;
+      break;
+    case rtmi::K32_SHADE:
+      if constexpr (has_shade(I)) return (const void*)f::k_shade_rays_f32<F>;
       break;
   }
   return nullptr;

@@ -127,6 +127,12 @@ __device__ __forceinline__ bool sort_point(const QueryParams& q, long long i, V3
     d = V3<double>{0.0, 0.0, 0.0};
     return __builtin_isfinite(pt.x) && __builtin_isfinite(pt.y);
   }
+  if (q.orig32) {  // float rays (rt_shade_rays_f32*): the same key, from the float values (widening is exact)
+    pt = V3<double>{(double)q.orig32[3 * i], (double)q.orig32[3 * i + 1], (double)q.orig32[3 * i + 2]};
+    d = V3<double>{(double)q.dir32[3 * i], (double)q.dir32[3 * i + 1], (double)q.dir32[3 * i + 2]};
+    const bool zero32 = d.x == 0.0 && d.y == 0.0 && d.z == 0.0;
+    return finite3(pt) && finite3(d) && !zero32;
+  }
   pt = V3<double>{q.orig[3 * i], q.orig[3 * i + 1], q.orig[3 * i + 2]};
   d = V3<double>{q.dir[3 * i], q.dir[3 * i + 1], q.dir[3 * i + 2]};
   const double tn = q.tnear ? q.tnear[i] : 0.0;

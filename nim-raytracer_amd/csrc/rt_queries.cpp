@@ -1,7 +1,7 @@
 // rt_queries.cpp — ray queries (rt_trace_rays* / rt_pick_pixels*): float64
 // closest hit, any hit and pixel picking on a scene, beside its render calls;
-// and radiance queries (rt_shade_rays*): the reference's colour along
-// caller-supplied rays.
+// and radiance queries: the reference's colour along caller-supplied rays in
+// float64 (rt_shade_rays*), the float32 render's in float32 (rt_shade_rays_f32*).
 #include <cmath>
 #include <cstring>
 
@@ -396,6 +396,144 @@ extern "C" int rt_shade_rays(rt_scene* s, const rt_options* o, int64_t n, const 
   if (int rc = shade_device(s, o, q, group, flags, d_rgb, d_rgb32, st, out)) return rc;
   if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
   if (rgb32) HIP_TRY(hipMemcpyAsync(rgb32, d_rgb32, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return RT_OK;
+}
+
+// ---- float32 radiance queries (rt_shade_rays_f32*) --------------------------
+namespace {
+
+// What both float32 shade entry points check before they take the scene's lock.
+int shade32_check(const rt_scene* s, const rt_options* o, int64_t n, int32_t group, uint32_t flags, const void* orig,
+                  const void* dir, const void* rgb) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (!o) return fail(RT_E_INVALID, "null options");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (flags & ~(uint32_t)RT_QUERY_SORT)
+    return fail(RT_E_INVALID, "rt_shade_rays_f32 takes RT_QUERY_SORT only (flags 0x%x)", flags);
+  if (group < 1) return fail(RT_E_INVALID, "group %d (at least 1)", group);
+  if (n % group) return fail(RT_E_INVALID, "%lld rays are not a whole number of groups of %d", (long long)n, group);
+  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n > 0 && !rgb) return fail(RT_E_INVALID, "null rgb");
+  if (o->precision != RT_FP32)
+    return fail(RT_E_INVALID, "rt_shade_rays_f32 is float32 only (precision %d): rt_shade_rays is the float64 query",
+                o->precision);
+  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
+  return RT_OK;
+}
+
+// The device body of both forms (the scene's lock held, its device current):
+// q.orig / q.dir and d_rgb are device memory.
+int shade32_device(rt_scene* s, const rt_options* o, Shade32Params q, int32_t group, uint32_t flags, float* d_rgb,
+                   hipStream_t st, rt_stats* out) {
+  // as check_options says it for a render (any_reflective: under the lock, rt_scene_set_objects may flip it)
+  if (s->any_reflective && o->max_ray_depth > kMaxShadeLevels - 1)
+    return fail(RT_E_UNSUPPORTED, "max_ray_depth %d > %d with reflective materials", o->max_ray_depth,
+                kMaxShadeLevels - 1);
+  // the scene's subset, as a render launches it (under the lock: rt_scene_set_lights / _set_objects flip bits)
+  const unsigned sub = s->f32_subset & ~(unsigned)SUB_STOCHASTIC & 63u;
+  // the scene words, bias, max_depth and the Stats rows; everything else
+  // stays zero: no camera, mapping or per-call word is reachable
+  FastParams p;
+  std::memset(&p, 0, sizeof p);
+  fast_scene_words(s, o->flags, p);
+  p.bias = (float)o->bias;
+  p.max_depth = o->max_ray_depth;
+  if (int rc = query_begin(s, st)) return rc;
+  p.partials = s->q_partials.p;
+  int& bpc = s->q_shade32_blocks_per_cu[sub];
+  if (bpc == 0) bpc = rtmi_shade_f32_blocks_per_cu(sub);
+  if (bpc <= 0)
+    return fail(RT_E_DEVICE, "the float32 radiance query kernel (subset %u) is not resident on this device", sub);
+  q.rgb = d_rgb;
+  if (group > 1) {
+    // the rays' colours, summed per group by k_shade_reduce32
+    const size_t need = (size_t)q.n * 3;
+    if (s->q_shade32.n < need) {
+      if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));  // an earlier query may still read the old buffer
+      if (int rc = s->q_shade32.alloc(need)) return rc;
+    }
+    q.rgb = s->q_shade32.p;
+  }
+  QueryParams qs{};  // RT_QUERY_SORT: the float-ray form of the keys
+  qs.orig32 = q.orig;
+  qs.dir32 = q.dir;
+  qs.n = q.n;
+  if (int rc = query_order(s, qs, flags, st)) return rc;
+  q.order = qs.order;
+  const int blocks = query_blocks(s, q.n, bpc);
+  if (const int e = rtmi_launch_shade_f32(&p, &q, sub, blocks, st))
+    return fail(RT_E_DEVICE, "float32 radiance query launch failed: %s", hipGetErrorString((hipError_t)e));
+  if (group > 1) {
+    if (const int e = rtmi_launch_shade_reduce32(q.rgb, q.n / group, group, (float)(1.0 / (double)group), d_rgb, st))
+      return fail(RT_E_DEVICE, "float32 radiance query group sum failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  unsigned long long h[kStatSlots];
+  if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
+  if (out) {
+    // one test per object per trace call (renderer.nim:54-56); the float32
+    // kernels leave the slot at 0 and the count is derived, as for a render
+    const unsigned long long rays = h[STAT_PRIMARY] + h[STAT_SHADOW] + h[STAT_REFL];
+    out->num_primary_rays = h[STAT_PRIMARY];
+    out->num_intersection_tests = (unsigned long long)s->nobj * rays;
+    out->num_intersection_hits = h[STAT_HITS];
+    out->num_shadow_rays = h[STAT_SHADOW];
+    out->num_reflection_rays = h[STAT_REFL];
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_shade_rays_f32_device(rt_scene* s, const rt_options* o, int64_t n, const float* d_orig,
+                                        const float* d_dir, int32_t group, uint32_t flags, float* d_rgb, void* stream,
+                                        rt_stats* out) {
+  if (int rc = shade32_check(s, o, n, group, flags, d_orig, d_dir, d_rgb)) return rc;
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  Shade32Params q{};
+  q.orig = d_orig;
+  q.dir = d_dir;
+  q.n = n;
+  return shade32_device(s, o, q, group, flags, d_rgb, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_shade_rays_f32(rt_scene* s, const rt_options* o, int64_t n, const float* orig, const float* dir,
+                                 int32_t group, uint32_t flags, float* rgb, rt_stats* out) {
+  if (int rc = shade32_check(s, o, n, group, flags, orig, dir, rgb)) return rc;
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  // the batch copied into the scene's staging buffer, shaded on the scene's
+  // own stream, the colours copied back (query_host's discipline)
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t v3 = (size_t)n * 3 * sizeof(float), ng = (size_t)(n / group);
+  const size_t off_dir = al(v3), off_rgb = off_dir + al(v3);
+  const size_t total = off_rgb + al(ng * 3 * sizeof(float));
+  hipStream_t st = s->stream;
+  if (s->q_stage.n < total) {
+    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+    if (int rc = s->q_stage.alloc(total)) return rc;
+  }
+  unsigned char* base = s->q_stage.p;
+  // the staging buffer's last user was a query on this stream, or has been waited for
+  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
+  HIP_TRY(hipMemcpyAsync(base, orig, v3, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(base + off_dir, dir, v3, hipMemcpyHostToDevice, st));
+  Shade32Params q{};
+  q.orig = (const float*)base;
+  q.dir = (const float*)(base + off_dir);
+  q.n = n;
+  float* d_rgb = (float*)(base + off_rgb);
+  if (int rc = shade32_device(s, o, q, group, flags, d_rgb, st, out)) return rc;
+  HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return RT_OK;
 }

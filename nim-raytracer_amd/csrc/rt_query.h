@@ -31,6 +31,10 @@ struct QueryParams {
   long long n;
   int32_t any_hit;       // RT_QUERY_ANY_HIT
   int32_t pad;
+  // rt_shade_rays_f32*: the batch's float rays (n * 3 each) for RT_QUERY_SORT's
+  // keys, instead of orig / dir; nullptr for every float64 query
+  const float* orig32;
+  const float* dir32;
 };
 
 // Where k_shade_rays leaves ray i's colour (rt_shade_rays*): three float64 at

@@ -77,6 +77,41 @@ unsigned f32_subset(const rt_scene* s, const rt_options* o) {
   return s->f32_subset | (o->aa_kind >= RT_AA_JITTERED ? SUB_STOCHASTIC : 0u);
 }
 
+void fast_scene_words(const rt_scene* s, uint32_t opt_flags, FastParams& p) {
+  p.objs = s->f32.objs.p;
+  p.objx = s->f32.objx.p;
+  p.meshes = s->f32.meshes.p;
+  p.lights = s->f32.lights.p;
+  p.tree = s->f32.tree.p;
+  p.normals = s->f32.normals.p;
+  for (int k = 0; k < 3; ++k) p.bg[k] = (float)s->bg[k];
+  p.nobj = s->nobj;
+  p.nlight = s->nlight;
+  p.has_point_light = s->has_point_light;
+  p.shadow_mesh = s->shadow_mesh;
+  // the shadow-ray records: on every path (binned or not), so every path
+  // tests a distant light's shadow rays with the same arithmetic
+  if (s->lrec.p) {
+    p.lrec_base = (uint64_t)(uintptr_t)s->lrec.p - (uint64_t)s->num_nodes * sizeof(TriFast);
+    p.lrec_stride = s->lrec_ntri * (int64_t)sizeof(LTri);
+    p.lrec_mask = s->lrec_mask;
+    p.grid_rec = s->grec.p;
+  }
+  // binned searches (rt_bins.h) of shadow rays to distant lights
+  if (!(opt_flags & RT_FLAG_NO_BINNING)) {
+    if (s->has_grids) {
+      p.grids = s->grids.p;
+      p.grid_off = s->grid_off.p;
+      p.grid_ent = s->grid_ent.p;
+    }
+    if (s->has_obj_grids) {
+      p.obj_grids = s->obj_grids.p;
+      p.obj_grid_mask = s->obj_grid_mask.p;
+      p.obj_off_grid = s->obj_off_grid;
+    }
+  }
+}
+
 }  // namespace rtmi
 
 namespace {
@@ -650,25 +685,17 @@ void plan_kernels(const rt_scene* s, const rt_options* o, const Mapping& mp, con
 int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, FastParams& p, Plan& pl,
               rt_scene::Order** measuring, hipStream_t st, bool* split, unsigned int* zero, int nzero, bool* zeroed) {
   std::memset(&p, 0, sizeof p);
-  p.objs = s->f32.objs.p;
-  p.objx = s->f32.objx.p;
-  p.meshes = s->f32.meshes.p;
-  p.lights = s->f32.lights.p;
-  p.tree = s->f32.tree.p;
-  p.normals = s->f32.normals.p;
+  // the scene, its shadow-ray records and (binned searches, rt_bins.h) the
+  // light and object grids of shadow rays to distant lights
+  fast_scene_words(s, o->flags, p);
   p.fb = fb;
   p.partials = s->partials.p;
   p.queue = s->queue.p;
   fast_camera(s->c2w, s->fov, o, p);
   const int spp = p.spp;
-  for (int k = 0; k < 3; ++k) p.bg[k] = (float)s->bg[k];
-  p.nobj = s->nobj;
-  p.nlight = s->nlight;
-  p.has_point_light = s->has_point_light;
   p.seed = o->seed;
   p.max_depth = o->max_ray_depth;
   p.flags = (int32_t)o->flags;
-  p.shadow_mesh = s->shadow_mesh;
   p.mode = mp.mode;
   p.y0 = mp.y0;
   p.nrows = mp.nrows;
@@ -708,29 +735,8 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
                    : flush_env > 0 ? flush_env
                                    : (int32_t)std::min<uint64_t>(1u << 20, std::max<uint64_t>(1, 0xFFFFFFFFull / per_item));
   }
-  // binned searches (rt_bins.h): camera rays when a wave spans at most 4
-  // pixels (>= 16 samples per pixel), shadow rays to distant lights
-  // the shadow-ray records: on every path (binned or not), so every path
-  // tests a distant light's shadow rays with the same arithmetic
-  if (s->lrec.p) {
-    p.lrec_base = (uint64_t)(uintptr_t)s->lrec.p - (uint64_t)s->num_nodes * sizeof(TriFast);
-    p.lrec_stride = s->lrec_ntri * (int64_t)sizeof(LTri);
-    p.lrec_mask = s->lrec_mask;
-    p.grid_rec = s->grec.p;
-  }
-  const bool binning = !(o->flags & RT_FLAG_NO_BINNING);
-  if (binning) {
-    if (s->has_grids) {
-      p.grids = s->grids.p;
-      p.grid_off = s->grid_off.p;
-      p.grid_ent = s->grid_ent.p;
-    }
-    if (s->has_obj_grids) {
-      p.obj_grids = s->obj_grids.p;
-      p.obj_grid_mask = s->obj_grid_mask.p;
-      p.obj_off_grid = s->obj_off_grid;
-    }
-  }
+  // (binned searches of camera rays, when a wave spans at most 4 pixels —
+  // >= 16 samples per pixel — are this call's own: frame_build below)
   // one work item per dequeue: per-pixel cost varies ~10x (sky vs bunny +
   // shadows), so coarser chunks leave an expensive tail in every launch
   // (C3 whole frame: 4 groups per dequeue 9.79 ms, 1 9.49 ms; 2-way bands:

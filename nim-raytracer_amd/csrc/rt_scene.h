@@ -275,6 +275,9 @@ struct rt_scene {
   // event discipline, and add:
   DevBuf<double> q_shade;                 // group > 1: the batch's per-ray colours (n * 3)
   int q_shade_blocks_per_cu[2] = {-1, -1};  // k_shade_rays' resident blocks per CU: one level, kMaxShadeLevels
+  // float32 radiance queries (rt_shade_rays_f32*), likewise:
+  DevBuf<float> q_shade32;                // group > 1: the batch's per-ray colours (n * 3)
+  int q_shade32_blocks_per_cu[64] = {};   // k_shade_rays_f32's resident blocks per CU by subset; 0: not asked yet
   int max_waves = 0;
   int64_t num_triangles = 0, num_nodes = 0;
   int max_depth = 0;
@@ -290,7 +293,8 @@ struct rt_scene {
                queue2.bytes() + f64_tables.bytes() + refl_queue.bytes() + refl_sec.bytes() + fb_scratch.bytes() +
                grids.bytes() + grid_off.bytes() + grid_ent.bytes() + obj_grids.bytes() + obj_grid_mask.bytes() +
                bin_dev.bytes() + sat_dev.bytes() + objbox_dev.bytes() + lrec.bytes() + grec.bytes() + fr.bytes() +
-               fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + q_shade.bytes() + refit_parent.bytes() +
+               fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + q_shade.bytes() + q_shade32.bytes() +
+               refit_parent.bytes() +
                refit_arrivals.bytes() + mesh_scratch.bytes();
     for (const MeshKeep& k : mesh_keep) b += k.verts.bytes() + k.faces.bytes() + k.order.bytes();
     for (const std::unique_ptr<Order>& o : orders) b += o->cost.bytes() + o->perm.bytes();
@@ -393,5 +397,11 @@ void refresh_host_lists(rt_scene* s);
 void uniform_cam(float ty, const float* light_vy, const FastParams& p, bg::UniformCam& u);
 void fast_camera(const double* c2w, double fov, const rt_options* o, FastParams& p);
 unsigned f32_subset(const rt_scene* s, const rt_options* o);
+// The words of a FastParams that depend on the scene alone: the geometry,
+// lights, tree and normals, bg, the counts, has_point_light, shadow_mesh, the
+// shadow-ray records and — unless opt_flags has RT_FLAG_NO_BINNING — the light
+// and object grids. fill_fast (a render call) and shade32_device (a float32
+// radiance query) both fill them here, so the two cannot drift apart.
+void fast_scene_words(const rt_scene* s, uint32_t opt_flags, FastParams& p);
 
 }  // namespace rtmi

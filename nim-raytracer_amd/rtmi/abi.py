@@ -253,6 +253,10 @@ SIGNATURES = {
     "rt_shade_rays": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                 C.c_int32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_float),
                                 C.POINTER(rt_stats)]),
+    "rt_shade_rays_f32_device": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, _P, _P, C.c_int32, C.c_uint32, _P,
+                                           _P, C.POINTER(rt_stats)]),
+    "rt_shade_rays_f32": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(rt_stats)]),
 }
 
 

@@ -254,6 +254,59 @@ class DeviceScene:
                                          p if f32 else None, _stream(stream), pst))
         return (rgb, Stats.from_c(st)) if stats else rgb
 
+    # -- float32 radiance queries (rt_shade_rays_f32*) ------------------------
+    def shade_rays_f32(self, opts: Options, orig, dir, group=1, sort=False, stats=False, stream=None):
+        """shade_rays in the float32 mode's arithmetic: the colour the fp32
+        render computes for a camera sample with each ray, for n
+        caller-supplied rays; the scene's own camera is not read. orig and
+        dir are (n, 3) float32 — numpy arrays (the host form) or CUDA torch
+        tensors (the device form, enqueued on `stream`; it waits only with
+        stats=True); dir as given, not normalised. Of opts bias, maxRayDepth,
+        precision (fp32) and of its flags RT_FLAG_NO_BINNING are read.
+        group=1: one colour per ray; group=g: the float32 sum of each run of
+        g colours in index order times float32(1 / g). Returns rgb as a
+        float32 (n / group, 3) array of the same kind, then the Stats when
+        asked. A degenerate ray (a non-finite component, a zero direction) is
+        (0, 0, 0) and counts nowhere; sort shades the rays in a coherence
+        order (the same answers)."""
+        flags = abi.RT_QUERY_SORT if sort else 0
+        group = int(group)
+        o = opts.to_c()
+        st = abi.rt_stats()
+        pst = C.byref(st) if stats else None
+        fp = C.POINTER(C.c_float)
+        if _is_host(orig):
+            og, d = _host_f32(orig), _host_f32(dir)
+            n = og.shape[0]
+            if d.shape[0] != n:
+                raise ValueError("orig and dir must hold the same number of rays")
+            ng = n // group if group >= 1 and n % group == 0 else 0  # (the library reports a bad group)
+            rgb = np.zeros((ng, 3), dtype=np.float32)
+            check(lib().rt_shade_rays_f32(self.h, C.byref(o), n, og.ctypes.data_as(fp), d.ctypes.data_as(fp), group,
+                                          flags, rgb.ctypes.data_as(fp), pst))
+            return (rgb, Stats.from_c(st)) if stats else rgb
+        import torch
+        n = _dev_f32(orig, None)
+        _dev_f32(dir, n)
+        ng = n // group if group >= 1 and n % group == 0 else 0
+        rgb = torch.empty((ng, 3), dtype=torch.float32, device=orig.device)
+        check(lib().rt_shade_rays_f32_device(self.h, C.byref(o), n, C.c_void_p(orig.data_ptr()),
+                                             C.c_void_p(dir.data_ptr()), group, flags, C.c_void_p(rgb.data_ptr()),
+                                             _stream(stream), pst))
+        return (rgb, Stats.from_c(st)) if stats else rgb
+
+    def shade32_subset(self):
+        """The specialisation of the float32 radiance-query kernel that
+        shade_rays_f32 launches on this scene: f32_subset's feature bits
+        without stochastic sampling."""
+        f = lib().rtmi_test_shade32_subset
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        r = f(self.h)
+        if r < 0:
+            raise RuntimeError("rtmi_test_shade32_subset failed")
+        return int(r)
+
     def _query_host(self, n, flags, normals, stats, call):
         hits = np.zeros(n, dtype=_HIT_DTYPE)
         nrm = np.zeros((n, 3), dtype=np.float64) if normals else None
@@ -874,6 +927,25 @@ def _is_host(a):
 
 def _host_f64(a, shape):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+
+
+def _host_f32(a):
+    """(n, 3) float32 rays; another dtype is refused (no silent rounding of float64 rays)."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise ValueError(f"float32 rays expected, got {a.dtype}")
+    return np.ascontiguousarray(a.reshape(-1, 3))
+
+
+def _dev_f32(t, n):
+    """Check a device array of n (or any number of) float32 rays; returns the ray count."""
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError("device arrays must be contiguous float32 CUDA/HIP tensors")
+    if t.numel() % 3 or (n is not None and t.numel() != n * 3):
+        raise ValueError(f"device array holds {t.numel()} floats, expected "
+                         f"{'a multiple of 3' if n is None else n * 3}")
+    return t.numel() // 3
 
 
 def _dptr(a):
