@@ -626,7 +626,8 @@ int rt_scene_last_mesh1(rt_scene *scene, int64_t *straight_batches);
  * for batches of caller-supplied rays and for picks through the camera:
  * what a GUI needs for the object under the mouse, a tool to place something
  * on a surface, a line-of-sight test. float64 only: the answers are the
- * reference's, operation for operation (there is no float32 mode).
+ * reference's, operation for operation (the float32 mode's hits:
+ * rt_trace_rays_f32 and rt_pick_pixels_f32 below).
  *
  * Ray i is the world-space (orig[3i..3i+2], 1), (dir[3i..3i+2], 0) of initRay
  * (geom.nim:41-48); dir is taken as given, NOT normalised, so t is in units
@@ -693,7 +694,8 @@ int rt_trace_rays(rt_scene *scene, int64_t n, const double *orig,
  * the akNone sample of that pixel; fractional coordinates and coordinates
  * outside the image are legal; a non-finite coordinate makes the ray
  * degenerate. Only width, height and precision of opts are read; precision
- * must be RT_FP64 (RT_E_UNSUPPORTED otherwise). flags, hits, normals and out
+ * must be RT_FP64 (RT_FP32 is RT_E_UNSUPPORTED here: rt_pick_pixels_f32 is
+ * the float32 render's pick). flags, hits, normals and out
  * as above; out->num_primary_rays is the number of rays that are not
  * degenerate. */
 int rt_pick_pixels_device(rt_scene *scene, const rt_options *opts, int64_t n,
@@ -814,6 +816,96 @@ int rt_shade_rays_f32_device(rt_scene *scene, const rt_options *opts, int64_t n,
 int rt_shade_rays_f32(rt_scene *scene, const rt_options *opts, int64_t n,
                       const float *orig, const float *dir, int32_t group,
                       uint32_t flags, float *rgb, rt_stats *out);
+
+/* ---- float32 ray queries -------------------------------------------------
+ * rt_trace_rays and rt_pick_pixels in the float32 mode's arithmetic: float32
+ * rays in (24 bytes per ray), 16-byte hits out, answered by the trace of the
+ * RT_FP32 render kernel. For line-of-sight, ambient-occlusion and placement
+ * batches whose answers feed float32 consumers, and for a front end that
+ * displays RT_FP32 frames: rt_pick_pixels_f32 forms its ray exactly as that
+ * render forms it, so the pick names the object the picture shows there
+ * (the float64 pick forms a float64 ray, and may disagree at a silhouette).
+ *
+ * Ray i is (orig[3i..], dir[3i..]), float32; dir is taken as given, NOT
+ * normalised, so t is in units of |dir|. t_near is n floats, or NULL for +inf
+ * for every ray. The answer is what the float32 render's trace computes for a
+ * ray with those values: the closest t with 0 <= t < t_near, the first object
+ * in scene order on equal t, the lowest face index on equal t within a mesh,
+ * the mesh AABB gate included (a ray that starts inside a mesh's box misses
+ * that mesh). Mesh faces are searched through the BVH: no pixel list or light
+ * grid of a render call is reachable. Accuracy is the float32 mode's
+ * (DESIGN.md "Float32 ray queries" quotes what was measured against
+ * rt_trace_rays on the same values).
+ *  - Miss: obj = -1, face = -1, t = that ray's t_near.
+ *  - RT_QUERY_ANY_HIT: trace as the float32 render's shadow rays call it, with
+ *    their exact early exit: only obj >= 0 versus obj == -1 is meaningful
+ *    (t echoes t_near, face is -1), and for every ray obj >= 0 exactly when
+ *    the closest-hit query's is. normals != NULL with this flag is
+ *    RT_E_INVALID.
+ *  - A degenerate ray — a non-finite component, an all-zero direction or a
+ *    NaN t_near — is answered as a miss with its t_near as given and adds
+ *    nothing to the Stats. A finite ray of any magnitude never faults; where
+ *    float32 arithmetic overflows, its answer is unspecified.
+ *  - normals (may be NULL) receives three floats per ray: the N the float32
+ *    render shades the hit with — normal(hitO) of a sphere, plane or box at
+ *    the float32 hit point, normals[face] of a mesh hit, through
+ *    objectToWorld for general transforms; not renormalised; (0, 0, 0) on a
+ *    miss.
+ *  - out (may be NULL): num_intersection_tests is the number of rays that are
+ *    not degenerate times the scene's object count, num_intersection_hits is
+ *    what the kernel counts, num_primary_rays is the number of rays that are
+ *    not degenerate for a pick and 0 for a trace; the other fields are 0. A
+ *    _device call with out == NULL only enqueues work on hip_stream; with out
+ *    it waits for the answers.
+ *  - RT_QUERY_SORT: as for rt_shade_rays_f32, the keys formed from the float
+ *    values (picks: from the float image positions); hits, normals and Stats
+ *    are the same, byte for byte.
+ *  - The answer and the Stats contribution of ray i depend on ray i, its
+ *    t_near and the scene only (picks: also on the camera, width and
+ *    height): not on n, the ray's index, its neighbours in the batch,
+ *    RT_QUERY_SORT, or the host versus the device form.
+ * Locking, ordering and edge cases are rt_trace_rays's: n == 0 is RT_OK with
+ * zero Stats; n < 0, unknown flag bits and null required pointers are
+ * RT_E_INVALID; n >= 2^31 is RT_E_UNSUPPORTED; everything rt_scene_last_*
+ * reports stays the last render call's. */
+typedef struct rt_hit32 {   /* 16 bytes */
+  float   t;                /* tHit; on a miss: that ray's t_near          */
+  int32_t obj;              /* index into rt_scene_desc.objects, -1 = nil  */
+  int32_t face;             /* original face index of a mesh hit, else -1  */
+  int32_t reserved;         /* written as 0                                */
+} rt_hit32;
+
+/* Device form: d_orig / d_dir (n*3 floats), d_tnear (n floats or NULL),
+ * d_hits (n rt_hit32, 16-byte aligned as device allocations are: RT_E_INVALID
+ * otherwise) and d_normals (n*3 floats or NULL) are device memory. */
+int rt_trace_rays_f32_device(rt_scene *scene, int64_t n, const float *d_orig,
+                             const float *d_dir, const float *d_tnear,
+                             uint32_t flags, rt_hit32 *d_hits, float *d_normals,
+                             void *hip_stream, rt_stats *out);
+/* Host form: the same arrays in caller memory (any alignment); returns with
+ * the answers. */
+int rt_trace_rays_f32(rt_scene *scene, int64_t n, const float *orig,
+                      const float *dir, const float *tnear, uint32_t flags,
+                      rt_hit32 *hits, float *normals, rt_stats *out);
+
+/* Float32 picking: ray i starts at the float32 camera origin and runs along
+ * the direction the RT_FP32 render forms for a sample at the float image
+ * position (xy[2i], xy[2i+1]) of a width x height frame, from the same folded
+ * float32 camera constants with the scene's current camera
+ * (rt_scene_set_camera applies), traced with t_near = +inf. Integer (x, y) is
+ * the akNone sample of that pixel, x + (i + 0.5) / m an akGrid sample;
+ * fractional coordinates and coordinates outside the image are legal; a
+ * non-finite coordinate makes the ray degenerate. Only width, height and
+ * precision of opts are read; precision must be RT_FP32 (RT_FP64 is
+ * RT_E_INVALID: rt_pick_pixels is the float64 pick). flags, hits, normals and
+ * out as above; out->num_primary_rays is the number of rays that are not
+ * degenerate. */
+int rt_pick_pixels_f32_device(rt_scene *scene, const rt_options *opts, int64_t n,
+                              const float *d_xy, uint32_t flags, rt_hit32 *d_hits,
+                              float *d_normals, void *hip_stream, rt_stats *out);
+int rt_pick_pixels_f32(rt_scene *scene, const rt_options *opts, int64_t n,
+                       const float *xy, uint32_t flags, rt_hit32 *hits,
+                       float *normals, rt_stats *out);
 
 /* ---- helpers ----------------------------------------------------------- */
 

@@ -406,6 +406,27 @@ struct Shade32Params {
   float* rgb;             // n * 3: ray i's colour at rgb[3 i] (group > 1: a temporary k_shade_reduce32 sums)
   long long n;
 };
+// rt_hit32 of include/rtmi.h: one float32 hit, written as one 16-byte store
+struct alignas(16) Hit32 {
+  float t;
+  int32_t obj, face, reserved;
+};
+static_assert(sizeof(Hit32) == 16, "rt_hit32 is 16 bytes");
+// One batch of a float32 ray query or pick (rt_trace_rays_f32* /
+// rt_pick_pixels_f32*, k_trace_rays_f32; all pointers device memory): the
+// kernel's second argument, after the FastParams.
+struct Trace32Params {
+  const float* orig;      // n * 3, or nullptr: picks
+  const float* dir;       // n * 3, as given
+  const float* tnear;     // n, or nullptr: +inf
+  const float* xy;        // picks: n * 2 float image positions
+  const uint32_t* order;  // RT_QUERY_SORT: slot k traces ray order[k]; nullptr: ray k
+  Hit32* hits;            // n, 16-byte aligned
+  float* normals;         // n * 3, or nullptr
+  long long n;
+  int32_t any_hit;        // RT_QUERY_ANY_HIT
+  int32_t pad;
+};
 // reflection queue of a k_render_wave wave: up to 63 rays left over plus a
 // pass's 64 new ones; fields ro xyz, rd xyz, weight, dst * 16 + depth
 constexpr int kReflQueue = 128, kReflFields = 9;
@@ -425,8 +446,9 @@ enum : unsigned {
 // the float32 kernel families of a feature subset: every subset has the
 // render kernel, some the lean / batched general pair or the
 // reflection-compacting kernel (rt_kernels_f32_part.hip); the non-stochastic
-// subsets also have the float32 radiance-query kernel (rt_fast_shade.h)
-enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3, K32_SHADE = 4 };
+// subsets also have the float32 radiance-query kernel (rt_fast_shade.h), the
+// 16 geometry subsets (bits 0..3) the float32 ray-query kernel (rt_fast_query.h)
+enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3, K32_SHADE = 4, K32_TRACE = 5 };
 // float32 kernel work queue: 64 head words, 128 B apart, zeroed per launch
 constexpr int kQueueShards = 64, kQueueStride = 32;
 // object-binned batches (k_render_fast, analytic scenes with distant lights,
@@ -473,6 +495,11 @@ int rtmi_launch_shade_f32(const rtmi::FastParams* p, const rtmi::Shade32Params* 
 int rtmi_shade_f32_blocks_per_cu(unsigned subset);
 int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int group, float inv_len, float* rgb,
                                void* stream);
+// k_trace_rays_f32 of a geometry subset (rt_fast_query.h; subset < 16: the
+// scene's sphere / box / mesh / general-transform bits)
+int rtmi_launch_trace_f32(const rtmi::FastParams* p, const rtmi::Trace32Params* q, unsigned subset, int blocks,
+                          void* stream);
+int rtmi_trace_f32_blocks_per_cu(unsigned subset);
 int rtmi_launch_ppm_encode(const float* fb, long long n, int bits, int srgb, void* out, void* stream);
 int rtmi_launch_rgba_encode(const float* fb, long long npix, unsigned int alpha, void* out, void* stream);
 // Sets this thread's rt_last_error() text; returns code (rtmi.cpp).

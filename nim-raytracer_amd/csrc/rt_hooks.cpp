@@ -73,6 +73,15 @@ extern "C" int rtmi_test_shade32_subset(rt_scene* s) {
   return (int)(s->f32_subset & ~(unsigned)SUB_STOCHASTIC & 63u);
 }
 
+// The specialisation of k_trace_rays_f32 a float32 ray query or pick
+// (rt_trace_rays_f32* / rt_pick_pixels_f32*) launches on this scene: the
+// scene's geometry bits, as trace32_device reads them.
+extern "C" int rtmi_test_trace32_subset(rt_scene* s) {
+  if (!s) return fail(RT_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  return (int)(s->f32_subset & 15u);
+}
+
 // Test hook: the LTri record (rt_common.h) of triangle v9 (v0, v1, v2 as 9
 // doubles, mesh object space) for the shadow direction d (float64), as
 // rt_scene_create builds it; out: 16 words.

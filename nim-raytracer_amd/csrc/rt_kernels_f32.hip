@@ -215,6 +215,22 @@ extern "C" int rtmi_shade_f32_blocks_per_cu(unsigned subset) {
   return blocks_per_cu(subset < 64u ? subset_kernel(rtmi::K32_SHADE, subset) : nullptr, 0, 0);
 }
 
+// The float32 ray-query kernel of a geometry subset (rt_fast_query.h): its
+// arguments are the FastParams, then the batch.
+extern "C" int rtmi_launch_trace_f32(const rtmi::FastParams* p, const rtmi::Trace32Params* q, unsigned subset,
+                                     int blocks, void* stream) {
+  const void* fn = subset < 16u ? subset_kernel(rtmi::K32_TRACE, subset) : nullptr;
+  if (!fn) return (int)hipErrorInvalidDeviceFunction;
+  void* args[] = {const_cast<rtmi::FastParams*>(p), const_cast<rtmi::Trace32Params*>(q)};
+  (void)hipLaunchKernel(fn, dim3(blocks), dim3(256), args, 0, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
+// Resident blocks per CU of the ray-query kernel; 0: none for the subset.
+extern "C" int rtmi_trace_f32_blocks_per_cu(unsigned subset) {
+  return blocks_per_cu(subset < 16u ? subset_kernel(rtmi::K32_TRACE, subset) : nullptr, 0, 0);
+}
+
 extern "C" int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int group, float inv_len,
                                           float* rgb, void* stream) {
   const unsigned blocks = (unsigned)((ngroups + 255) / 256);

@@ -7,6 +7,7 @@
 // without the sphere / box / rotation / point-light / reflection code paths
 // (fewer branches, fewer SALU, 66 instead of 72+ VGPRs).
 #include "rt_fast.h"
+#include "rt_fast_query.h"
 #include "rt_fast_shade.h"
 
 #ifndef RTMI_PART
@@ -33,6 +34,9 @@ constexpr bool has_wave(unsigned i) { return (i & 32u) != 0u; }
 // the float32 radiance-query kernel reads its rays from memory: it exists for
 // the subsets without stochastic sampling
 constexpr bool has_shade(unsigned i) { return (i & 64u) == 0u; }
+// the float32 ray-query kernel depends on the geometry bits alone: it exists
+// for the 16 subsets of {sphere, box, mesh, general transform} (parts 0 and 1)
+constexpr bool has_trace(unsigned i) { return i < 16u; }
 
 // The host address of kernel (family, subset I), null where the family has
 // none for the subset. Taking an address instantiates the kernel.
@@ -53,6 +57,9 @@ const void* kernel_of(int family) {
       break;
     case rtmi::K32_SHADE:
       if constexpr (has_shade(I)) return (const void*)f::k_shade_rays_f32<F>;
+      break;
+    case rtmi::K32_TRACE:
+      if constexpr (has_trace(I)) return (const void*)f::k_trace_rays_f32<F>;
       break;
   }
   return nullptr;

@@ -127,11 +127,17 @@ __device__ __forceinline__ bool sort_point(const QueryParams& q, long long i, V3
     d = V3<double>{0.0, 0.0, 0.0};
     return __builtin_isfinite(pt.x) && __builtin_isfinite(pt.y);
   }
-  if (q.orig32) {  // float rays (rt_shade_rays_f32*): the same key, from the float values (widening is exact)
+  if (q.xy32) {  // float picks (rt_pick_pixels_f32*): the pick's key, from the float positions
+    pt = V3<double>{(double)q.xy32[2 * i], (double)q.xy32[2 * i + 1], 0.0};
+    d = V3<double>{0.0, 0.0, 0.0};
+    return __builtin_isfinite(pt.x) && __builtin_isfinite(pt.y);
+  }
+  if (q.orig32) {  // float rays (rt_shade_rays_f32*, rt_trace_rays_f32*): the same key, from the float values (widening is exact)
     pt = V3<double>{(double)q.orig32[3 * i], (double)q.orig32[3 * i + 1], (double)q.orig32[3 * i + 2]};
     d = V3<double>{(double)q.dir32[3 * i], (double)q.dir32[3 * i + 1], (double)q.dir32[3 * i + 2]};
+    const float tn32 = q.tnear32 ? q.tnear32[i] : 0.0f;
     const bool zero32 = d.x == 0.0 && d.y == 0.0 && d.z == 0.0;
-    return finite3(pt) && finite3(d) && !zero32;
+    return finite3(pt) && finite3(d) && !zero32 && !(tn32 != tn32);
   }
   pt = V3<double>{q.orig[3 * i], q.orig[3 * i + 1], q.orig[3 * i + 2]};
   d = V3<double>{q.dir[3 * i], q.dir[3 * i + 1], q.dir[3 * i + 2]};
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(256) void k_query_keys(const QueryParams q, const u
     V3<double> pt, d;
     uint32_t k = 0xffffffffu;
     if (sort_point(q, i, pt, d)) {
-      if (q.xy) {
+      if (q.xy || q.xy32) {
         k = spread2(quant(pt.x, lo[0], hi[0], 1 << 15)) | (spread2(quant(pt.y, lo[1], hi[1], 1 << 15)) << 1);
       } else {
         const uint32_t oct = (d.x < 0.0 ? 1u : 0u) | (d.y < 0.0 ? 2u : 0u) | (d.z < 0.0 ? 4u : 0u);

@@ -1,7 +1,9 @@
 // rt_queries.cpp — ray queries (rt_trace_rays* / rt_pick_pixels*): float64
 // closest hit, any hit and pixel picking on a scene, beside its render calls;
 // and radiance queries: the reference's colour along caller-supplied rays in
-// float64 (rt_shade_rays*), the float32 render's in float32 (rt_shade_rays_f32*).
+// float64 (rt_shade_rays*), the float32 render's in float32 (rt_shade_rays_f32*);
+// and the float32 render's trace for float32 rays and picks
+// (rt_trace_rays_f32* / rt_pick_pixels_f32*).
 #include <cmath>
 #include <cstring>
 
@@ -536,4 +538,200 @@ extern "C" int rt_shade_rays_f32(rt_scene* s, const rt_options* o, int64_t n, co
   HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return RT_OK;
+}
+
+// ---- float32 ray queries and picks (rt_trace_rays_f32* / rt_pick_pixels_f32*) ----
+static_assert(sizeof(rt_hit32) == sizeof(Hit32), "rt_hit32 layout");
+
+namespace {
+
+// What every float32 hit query checks before it takes the scene's lock.
+int trace32_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, const void* normals) {
+  if (!s) return fail(RT_E_INVALID, "null scene");
+  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
+  if (flags & ~kQueryFlags) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags & ~kQueryFlags);
+  if ((flags & RT_QUERY_ANY_HIT) && normals)
+    return fail(RT_E_INVALID, "normals are not available with RT_QUERY_ANY_HIT");
+  if (n > 0 && !hits) return fail(RT_E_INVALID, "null hits");
+  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
+  return RT_OK;
+}
+
+int pick32_check(const rt_options* o) {
+  if (!o) return fail(RT_E_INVALID, "null options");
+  if (o->width <= 0 || o->height <= 0 || o->width > 65536 || o->height > 65536)
+    return fail(RT_E_INVALID, "bad image size %dx%d", o->width, o->height);
+  if (o->precision != RT_FP32)
+    return fail(RT_E_INVALID, "rt_pick_pixels_f32 is float32 only (precision %d): rt_pick_pixels is the float64 pick",
+                o->precision);
+  return RT_OK;
+}
+
+// The device body of every float32 hit query (the scene's lock held, its
+// device current): q's ray, hit and normal pointers are device memory. pick:
+// the image size of a pick (its width and height alone are read), nullptr for
+// a trace.
+int trace32_device(rt_scene* s, const rt_options* pick, Trace32Params q, uint32_t flags, hipStream_t st,
+                   rt_stats* out) {
+  if ((uintptr_t)q.hits & 15u) return fail(RT_E_INVALID, "hits must be 16-byte aligned device memory");
+  // trace reads the geometry bits alone (under the lock: rt_scene_set_objects may flip them)
+  const unsigned sub = s->f32_subset & 15u;
+  // the scene words and the Stats rows, for picks the render's camera
+  // constants; everything else stays zero: no grid, mapping or per-call word
+  // is reachable (pix = -1, light = -1)
+  FastParams p;
+  std::memset(&p, 0, sizeof p);
+  if (pick) {
+    rt_options oc{};
+    oc.width = pick->width;
+    oc.height = pick->height;
+    oc.aa_kind = RT_AA_NONE;
+    fast_camera(s->c2w, s->fov, &oc, p);
+  }
+  fast_scene_words(s, RT_FLAG_NO_BINNING, p);
+  if (int rc = query_begin(s, st)) return rc;
+  p.partials = s->q_partials.p;
+  int& bpc = s->q_trace32_blocks_per_cu[sub];
+  if (bpc == 0) bpc = rtmi_trace_f32_blocks_per_cu(sub);
+  if (bpc <= 0)
+    return fail(RT_E_DEVICE, "the float32 ray query kernel (subset %u) is not resident on this device", sub);
+  q.any_hit = (flags & RT_QUERY_ANY_HIT) ? 1 : 0;
+  QueryParams qs{};  // RT_QUERY_SORT: the float forms of the keys
+  qs.orig32 = q.orig;
+  qs.dir32 = q.dir;
+  qs.tnear32 = q.tnear;
+  qs.xy32 = q.xy;
+  qs.n = q.n;
+  if (int rc = query_order(s, qs, flags, st)) return rc;
+  q.order = qs.order;
+  const int blocks = query_blocks(s, q.n, bpc);
+  if (const int e = rtmi_launch_trace_f32(&p, &q, sub, blocks, st))
+    return fail(RT_E_DEVICE, "float32 ray query launch failed: %s", hipGetErrorString((hipError_t)e));
+  unsigned long long h[kStatSlots];
+  if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
+  if (out) {
+    // one test per object per trace call (renderer.nim:54-56): derived, as
+    // shade32_device derives it; camera rays are a pick's
+    *out = rt_stats{};
+    out->num_primary_rays = pick ? h[STAT_PRIMARY] : 0;
+    out->num_intersection_tests = (unsigned long long)s->nobj * h[STAT_PRIMARY];
+    out->num_intersection_hits = h[STAT_HITS];
+  }
+  return RT_OK;
+}
+
+// Host form: the batch copied into the scene's staging buffer, queried on the
+// scene's own stream, the answers copied back (query_host's discipline).
+// in[k]: host arrays of in_bytes[k] bytes (nullptr: absent): orig, dir, tnear, xy.
+int trace32_host(rt_scene* s, const rt_options* pick, int64_t n, const void* const in[4], const size_t in_bytes[4],
+                 uint32_t flags, rt_hit32* hits, float* normals, rt_stats* out) {
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  size_t off[6], total = 0;
+  for (int k = 0; k < 4; ++k) {
+    off[k] = total;
+    total += in[k] ? al(in_bytes[k]) : 0;
+  }
+  off[4] = total;
+  total += al((size_t)n * sizeof(rt_hit32));
+  off[5] = total;
+  total += normals ? al((size_t)n * 3 * sizeof(float)) : 0;
+  hipStream_t st = s->stream;
+  if (s->q_stage.n < total) {
+    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
+    if (int rc = s->q_stage.alloc(total)) return rc;
+  }
+  unsigned char* base = s->q_stage.p;
+  // the staging buffer's last user was a query on this stream, or has been waited for
+  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
+  for (int k = 0; k < 4; ++k)
+    if (in[k]) HIP_TRY(hipMemcpyAsync(base + off[k], in[k], in_bytes[k], hipMemcpyHostToDevice, st));
+  Trace32Params q{};
+  q.orig = in[0] ? (const float*)(base + off[0]) : nullptr;
+  q.dir = in[1] ? (const float*)(base + off[1]) : nullptr;
+  q.tnear = in[2] ? (const float*)(base + off[2]) : nullptr;
+  q.xy = in[3] ? (const float*)(base + off[3]) : nullptr;
+  q.hits = (Hit32*)(base + off[4]);
+  q.normals = normals ? (float*)(base + off[5]) : nullptr;
+  q.n = n;
+  if (int rc = trace32_device(s, pick, q, flags, st, out)) return rc;
+  HIP_TRY(hipMemcpyAsync(hits, base + off[4], (size_t)n * sizeof(rt_hit32), hipMemcpyDeviceToHost, st));
+  if (normals)
+    HIP_TRY(hipMemcpyAsync(normals, base + off[5], (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_trace_rays_f32_device(rt_scene* s, int64_t n, const float* d_orig, const float* d_dir,
+                                        const float* d_tnear, uint32_t flags, rt_hit32* d_hits, float* d_normals,
+                                        void* stream, rt_stats* out) {
+  if (int rc = trace32_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  Trace32Params q{};
+  q.orig = d_orig;
+  q.dir = d_dir;
+  q.tnear = d_tnear;
+  q.hits = (Hit32*)d_hits;
+  q.normals = d_normals;
+  q.n = n;
+  return trace32_device(s, nullptr, q, flags, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_trace_rays_f32(rt_scene* s, int64_t n, const float* orig, const float* dir, const float* tnear,
+                                 uint32_t flags, rt_hit32* hits, float* normals, rt_stats* out) {
+  if (int rc = trace32_check(s, n, flags, hits, normals)) return rc;
+  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  const size_t v3 = (size_t)n * 3 * sizeof(float);
+  const void* const in[4] = {orig, dir, tnear, nullptr};
+  const size_t bytes[4] = {v3, v3, (size_t)n * sizeof(float), 0};
+  return trace32_host(s, nullptr, n, in, bytes, flags, hits, normals, out);
+}
+
+extern "C" int rt_pick_pixels_f32_device(rt_scene* s, const rt_options* o, int64_t n, const float* d_xy,
+                                         uint32_t flags, rt_hit32* d_hits, float* d_normals, void* stream,
+                                         rt_stats* out) {
+  if (int rc = trace32_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (int rc = pick32_check(o)) return rc;
+  if (n > 0 && !d_xy) return fail(RT_E_INVALID, "null pixel positions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  Trace32Params q{};
+  q.xy = d_xy;
+  q.hits = (Hit32*)d_hits;
+  q.normals = d_normals;
+  q.n = n;
+  return trace32_device(s, o, q, flags, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_pick_pixels_f32(rt_scene* s, const rt_options* o, int64_t n, const float* xy, uint32_t flags,
+                                  rt_hit32* hits, float* normals, rt_stats* out) {
+  if (int rc = trace32_check(s, n, flags, hits, normals)) return rc;
+  if (int rc = pick32_check(o)) return rc;
+  if (n > 0 && !xy) return fail(RT_E_INVALID, "null pixel positions");
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  const void* const in[4] = {nullptr, nullptr, nullptr, xy};
+  const size_t bytes[4] = {0, 0, 0, (size_t)n * 2 * sizeof(float)};
+  return trace32_host(s, o, n, in, bytes, flags, hits, normals, out);
 }

@@ -35,6 +35,11 @@ struct QueryParams {
   // keys, instead of orig / dir; nullptr for every float64 query
   const float* orig32;
   const float* dir32;
+  // rt_trace_rays_f32*: the rays' float t_near (n, or nullptr: +inf) beside
+  // orig32 / dir32; rt_pick_pixels_f32*: the float image positions (n * 2)
+  // instead of xy
+  const float* tnear32;
+  const float* xy32;
 };
 
 // Where k_shade_rays leaves ray i's colour (rt_shade_rays*): three float64 at

@@ -278,6 +278,8 @@ struct rt_scene {
   // float32 radiance queries (rt_shade_rays_f32*), likewise:
   DevBuf<float> q_shade32;                // group > 1: the batch's per-ray colours (n * 3)
   int q_shade32_blocks_per_cu[64] = {};   // k_shade_rays_f32's resident blocks per CU by subset; 0: not asked yet
+  // float32 ray queries and picks (rt_trace_rays_f32* / rt_pick_pixels_f32*), likewise:
+  int q_trace32_blocks_per_cu[16] = {};   // k_trace_rays_f32's resident blocks per CU by geometry subset; 0: not asked yet
   int max_waves = 0;
   int64_t num_triangles = 0, num_nodes = 0;
   int max_depth = 0;

@@ -141,6 +141,15 @@ class rt_hit(C.Structure):
     ]
 
 
+class rt_hit32(C.Structure):
+    _fields_ = [
+        ("t", C.c_float),
+        ("obj", C.c_int32),
+        ("face", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 RT_QUEUE_STOPPED, RT_QUEUE_RUNNING, RT_QUEUE_SHUTDOWN = 0, 1, 2
 
 
@@ -257,6 +266,13 @@ SIGNATURES = {
                                            _P, C.POINTER(rt_stats)]),
     "rt_shade_rays_f32": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                     C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(rt_stats)]),
+    "rt_trace_rays_f32_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(rt_stats)]),
+    "rt_trace_rays_f32": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.c_uint32, C.POINTER(rt_hit32), C.POINTER(C.c_float), C.POINTER(rt_stats)]),
+    "rt_pick_pixels_f32_device": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, _P, C.c_uint32, _P, _P, _P,
+                                            C.POINTER(rt_stats)]),
+    "rt_pick_pixels_f32": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_float), C.c_uint32,
+                                     C.POINTER(rt_hit32), C.POINTER(C.c_float), C.POINTER(rt_stats)]),
 }
 
 

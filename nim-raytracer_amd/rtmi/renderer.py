@@ -307,6 +307,90 @@ class DeviceScene:
             raise RuntimeError("rtmi_test_shade32_subset failed")
         return int(r)
 
+    # -- float32 ray queries (rt_trace_rays_f32* / rt_pick_pixels_f32*) ------
+    def trace_rays_f32(self, orig, dir, t_near=None, any_hit=False, sort=False, normals=False, stats=False,
+                       stream=None):
+        """trace_rays in the float32 mode's arithmetic: what the fp32 render's
+        trace answers for n caller-supplied rays. orig and dir are (n, 3)
+        float32 — numpy arrays (the host form) or CUDA torch tensors (the
+        device form, enqueued on `stream`; it waits only with stats=True) —
+        dir as given, not normalised; t_near (n,) float32 or None for +inf.
+        Returns (t, obj, face[, normals][, Stats]) as arrays of the same
+        kind, t and the normals float32: t is the ray's t_near and obj / face
+        are -1 on a miss; with any_hit only obj >= 0 / obj == -1 is
+        meaningful; sort traces the rays in a coherence order (the same
+        answers); normals: the N the fp32 render shades the hit with,
+        (0, 0, 0) on a miss. The device form's t / obj / face are views of
+        one (n, 4) float32 tensor."""
+        flags = (abi.RT_QUERY_ANY_HIT if any_hit else 0) | (abi.RT_QUERY_SORT if sort else 0)
+        if _is_host(orig):
+            o, d = _host_f32(orig), _host_f32(dir)
+            n = o.shape[0]
+            if d.shape[0] != n:
+                raise ValueError("orig and dir must hold the same number of rays")
+            tn = None if t_near is None else _host_f32n(t_near, 1)
+            if tn is not None and tn.shape[0] != n:
+                raise ValueError("t_near must hold one value per ray")
+            return self._query32_host(n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32(
+                self.h, n, _fptr(o), _fptr(d), _fptr(tn), flags, hits, nrm, st))
+        n = _dev_f32(orig, None)
+        _dev_f32(dir, n)
+        if t_near is not None:
+            _dev_f32n(t_near, n, 1)
+        return self._query32_device(orig, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32_device(
+            self.h, n, C.c_void_p(orig.data_ptr()), C.c_void_p(dir.data_ptr()),
+            C.c_void_p(t_near.data_ptr()) if t_near is not None else None, flags, hits, nrm, _stream(stream), st))
+
+    def pick_f32(self, opts: Options, xy, any_hit=False, sort=False, normals=False, stats=False, stream=None):
+        """What the fp32 render shows at image position xy[i] = (x, y): the
+        ray that render forms for a sample there (the scene's current camera,
+        an opts.width x opts.height image; opts.precision must be fp32),
+        traced with t_near = +inf. Integer (x, y) is the akNone sample of
+        that pixel; fractional and out-of-image positions are legal. xy is
+        (n, 2) float32, numpy or CUDA torch; returns as trace_rays_f32 does,
+        the Stats' numPrimaryRays counting the rays that are not degenerate."""
+        flags = (abi.RT_QUERY_ANY_HIT if any_hit else 0) | (abi.RT_QUERY_SORT if sort else 0)
+        o = opts.to_c()
+        if _is_host(xy):
+            p = _host_f32n(xy, 2)
+            n = p.shape[0]
+            return self._query32_host(n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32(
+                self.h, C.byref(o), n, _fptr(p), flags, hits, nrm, st))
+        n = _dev_f32n(xy, None, 2)
+        return self._query32_device(xy, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32_device(
+            self.h, C.byref(o), n, C.c_void_p(xy.data_ptr()), flags, hits, nrm, _stream(stream), st))
+
+    def trace32_subset(self):
+        """The specialisation of the float32 ray-query kernel that
+        trace_rays_f32 and pick_f32 launch on this scene: f32_subset's four
+        geometry bits."""
+        f = lib().rtmi_test_trace32_subset
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        r = f(self.h)
+        if r < 0:
+            raise RuntimeError("rtmi_test_trace32_subset failed")
+        return int(r)
+
+    def _query32_host(self, n, normals, stats, call):
+        hits = np.zeros(n, dtype=_HIT32_DTYPE)
+        nrm = np.zeros((n, 3), dtype=np.float32) if normals else None
+        st = abi.rt_stats()
+        check(call(hits.ctypes.data_as(C.POINTER(abi.rt_hit32)), _fptr(nrm), C.byref(st) if stats else None))
+        out = (hits["t"].copy(), hits["obj"].copy(), hits["face"].copy())
+        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
+
+    def _query32_device(self, like, n, normals, stats, call):
+        import torch
+        hits = torch.empty((n, 4), dtype=torch.float32, device=like.device)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=like.device) if normals else None
+        st = abi.rt_stats()
+        check(call(C.c_void_p(hits.data_ptr()), C.c_void_p(nrm.data_ptr()) if normals else None,
+                   C.byref(st) if stats else None))
+        words = hits.view(torch.int32)
+        out = (hits[:, 0], words[:, 1], words[:, 2])
+        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
+
     def _query_host(self, n, flags, normals, stats, call):
         hits = np.zeros(n, dtype=_HIT_DTYPE)
         nrm = np.zeros((n, 3), dtype=np.float64) if normals else None
@@ -918,6 +1002,8 @@ def _ptr(buf, min_floats):
 
 # rt_hit (include/rtmi.h) as a numpy record
 _HIT_DTYPE = np.dtype([("t", np.float64), ("obj", np.int32), ("face", np.int32)])
+# rt_hit32 likewise
+_HIT32_DTYPE = np.dtype([("t", np.float32), ("obj", np.int32), ("face", np.int32), ("reserved", np.int32)])
 
 
 def _is_host(a):
@@ -946,6 +1032,29 @@ def _dev_f32(t, n):
         raise ValueError(f"device array holds {t.numel()} floats, expected "
                          f"{'a multiple of 3' if n is None else n * 3}")
     return t.numel() // 3
+
+
+def _host_f32n(a, width):
+    """(n, width) float32 rows ((n,) for width 1); another dtype is refused."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise ValueError(f"float32 values expected, got {a.dtype}")
+    return np.ascontiguousarray(a.reshape(-1) if width == 1 else a.reshape(-1, width))
+
+
+def _dev_f32n(t, n, width):
+    """Check a device array of n (or any number of) rows of `width` float32; returns the row count."""
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError("device arrays must be contiguous float32 CUDA/HIP tensors")
+    if t.numel() % width or (n is not None and t.numel() != n * width):
+        raise ValueError(f"device array holds {t.numel()} floats, expected "
+                         f"{'a multiple of ' + str(width) if n is None else n * width}")
+    return t.numel() // width
+
+
+def _fptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def _dptr(a):
