@@ -907,6 +907,67 @@ int rt_pick_pixels_f32(rt_scene *scene, const rt_options *opts, int64_t n,
                        const float *xy, uint32_t flags, rt_hit32 *hits,
                        float *normals, rt_stats *out);
 
+/* ---- feature buffers ------------------------------------------------------
+ * The per-pixel feature buffers (AOVs) of an RT_FP32 frame: coverage, depth,
+ * object / face id, normal and albedo, taken over the frame's own samples —
+ * alpha for compositing, albedo and normal to guide a denoiser, depth for a
+ * post-pass, the ids for a selection outline. One call traces the frame's
+ * camera rays and shades nothing.
+ *
+ * Pixel (x, y) of rows [y0, y1), sample s, is the RT_FP32 render's for the
+ * same width, height, aa_kind, grid_size and seed (every sampler; akGrid
+ * sample s = sj*m + si sits at (x + (si+.5)/m, y + (sj+.5)/m) in float32).
+ * Its ray starts at the float32 camera origin and runs along the render's
+ * normalised direction, so depth is the distance from the camera. Its hit is
+ * what rt_pick_pixels_f32 returns at that image position, bit for bit: t,
+ * obj, face and normal. inv_len is the render's (float)(1.0 / (double)spp),
+ * exactly 1 for RT_AA_NONE.
+ *  - opts: width, height, aa_kind, grid_size, seed, precision and flags are
+ *    read; bias and max_ray_depth are not. precision must be RT_FP32 (RT_FP64
+ *    is RT_E_UNSUPPORTED); the sampler limits are a render's (grid_size
+ *    outside [1, 256] is RT_E_INVALID, a (multi-)jittered grid_size above 32
+ *    RT_E_UNSUPPORTED). Of flags only RT_FLAG_NO_BINNING is honoured: the
+ *    camera rays then search the BVH instead of this call's per-pixel face
+ *    lists and object masks. Every channel is byte-identical either way.
+ *  - Rows outside [y0, y1) and NULL channels are never written. A pixel none
+ *    of whose samples hits gets alpha 0, depth +inf, ids -1 and sums +0.
+ *  - out (may be NULL): num_primary_rays is the number of samples traced,
+ *    num_intersection_tests that times the object count,
+ *    num_intersection_hits what the kernel counts (rt_pick_pixels_f32's over
+ *    the same positions); shadow and reflection counts are 0. A _device call
+ *    with out == NULL only enqueues work on hip_stream.
+ *  - A render-class call: it takes the scene's lock, is ordered after the
+ *    scene's calls in flight, and afterwards rt_scene_last_stats returns its
+ *    Stats while the other rt_scene_last_* readers report nothing classified,
+ *    as after an RT_FP64 render. It measures and consumes no launch order,
+ *    and the next colour render gives the bytes, Stats and diagnostics it
+ *    would have given without this call.
+ *  - RT_E_INVALID: a null scene, opts or buffer struct; every channel NULL
+ *    with y1 > y0; rows outside [0, height]. y0 == y1 is RT_OK and launches
+ *    nothing. No argument error touches the device. */
+
+/* Every pointer is width*height elements (x3 where noted), row-major as the
+ * framebuffer, or NULL = not wanted. */
+typedef struct rt_aov_buffers {
+  float   *alpha;   /* hits * inv_len: hits = samples whose camera ray hits an object */
+  float   *depth;   /* smallest tHit over the pixel's samples; +inf when none hits */
+  int32_t *object;  /* rt_hit32.obj of the sample with the smallest (tHit, sample index); -1 */
+  int32_t *face;    /* rt_hit32.face of that sample; -1 */
+  float   *normal;  /* x3: float32 sum, from +0, over the hitting samples of the N the
+                       float32 render shades the hit with (what rt_pick_pixels_f32 returns:
+                       not renormalised), times inv_len */
+  float   *albedo;  /* x3: the same sum of (float)rt_object_desc.albedo[c] of the hit object,
+                       times inv_len */
+} rt_aov_buffers;
+
+/* Device form: the channels are device memory. */
+int rt_render_aovs_device(rt_scene *scene, const rt_options *opts, const rt_aov_buffers *d_out,
+                          int32_t y0, int32_t y1, void *hip_stream, rt_stats *out);
+/* Host form: the channels are caller memory, staged through device buffers;
+ * returns with the answers. */
+int rt_render_aovs(rt_scene *scene, const rt_options *opts, const rt_aov_buffers *out_bufs,
+                   int32_t y0, int32_t y1, rt_stats *out);
+
 /* ---- helpers ----------------------------------------------------------- */
 
 /* glm-style inverse of a column-major 4x4 (what geom.nim's

@@ -427,6 +427,19 @@ struct Trace32Params {
   int32_t any_hit;        // RT_QUERY_ANY_HIT
   int32_t pad;
 };
+// The outputs of a feature-buffer call (rt_render_aovs*, k_render_aov; all
+// pointers device memory): the kernel's second argument, after the FastParams.
+// The six channels are rt_aov_buffers' (width * height elements, x 3 for
+// normal and albedo; nullptr: not wanted).
+struct Aov32Params {
+  float* alpha;
+  float* depth;
+  int32_t* object;
+  int32_t* face;
+  float* normal;
+  float* albedo;
+  const float* obj_albedo;  // nobj * 3: (float)rt_object_desc.albedo (rt_scene::albedo32)
+};
 // reflection queue of a k_render_wave wave: up to 63 rays left over plus a
 // pass's 64 new ones; fields ro xyz, rd xyz, weight, dst * 16 + depth
 constexpr int kReflQueue = 128, kReflFields = 9;
@@ -447,8 +460,10 @@ enum : unsigned {
 // render kernel, some the lean / batched general pair or the
 // reflection-compacting kernel (rt_kernels_f32_part.hip); the non-stochastic
 // subsets also have the float32 radiance-query kernel (rt_fast_shade.h), the
-// 16 geometry subsets (bits 0..3) the float32 ray-query kernel (rt_fast_query.h)
-enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3, K32_SHADE = 4, K32_TRACE = 5 };
+// 16 geometry subsets (bits 0..3) the float32 ray-query kernel
+// (rt_fast_query.h), and those 16 with and without stochastic sampling the
+// feature-buffer kernel (rt_fast_aov.h)
+enum : int { K32_FAST = 0, K32_LEAN = 1, K32_GEN = 2, K32_WAVE = 3, K32_SHADE = 4, K32_TRACE = 5, K32_AOV = 6 };
 // float32 kernel work queue: 64 head words, 128 B apart, zeroed per launch
 constexpr int kQueueShards = 64, kQueueStride = 32;
 // object-binned batches (k_render_fast, analytic scenes with distant lights,
@@ -500,6 +515,11 @@ int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int grou
 int rtmi_launch_trace_f32(const rtmi::FastParams* p, const rtmi::Trace32Params* q, unsigned subset, int blocks,
                           void* stream);
 int rtmi_trace_f32_blocks_per_cu(unsigned subset);
+// k_render_aov of a geometry subset with or without stochastic sampling
+// (rt_fast_aov.h; subset & ~(15 | SUB_STOCHASTIC) must be 0)
+int rtmi_launch_aov_f32(const rtmi::FastParams* p, const rtmi::Aov32Params* q, unsigned subset, int blocks,
+                        size_t shmem, void* stream);
+int rtmi_aov_f32_blocks_per_cu(unsigned subset, size_t shmem);
 int rtmi_launch_ppm_encode(const float* fb, long long n, int bits, int srgb, void* out, void* stream);
 int rtmi_launch_rgba_encode(const float* fb, long long npix, unsigned int alpha, void* out, void* stream);
 // Sets this thread's rt_last_error() text; returns code (rtmi.cpp).

@@ -231,6 +231,28 @@ extern "C" int rtmi_trace_f32_blocks_per_cu(unsigned subset) {
   return blocks_per_cu(subset < 16u ? subset_kernel(rtmi::K32_TRACE, subset) : nullptr, 0, 0);
 }
 
+// The feature-buffer kernel of a geometry subset, with or without stochastic
+// sampling (rt_fast_aov.h): its arguments are the FastParams, then the outputs.
+namespace {
+const void* aov_kernel(unsigned subset) {
+  return (subset & ~(15u | (unsigned)rtmi::SUB_STOCHASTIC)) == 0u ? subset_kernel(rtmi::K32_AOV, subset) : nullptr;
+}
+}  // namespace
+
+extern "C" int rtmi_launch_aov_f32(const rtmi::FastParams* p, const rtmi::Aov32Params* q, unsigned subset, int blocks,
+                                   size_t shmem, void* stream) {
+  const void* fn = aov_kernel(subset);
+  if (!fn) return (int)hipErrorInvalidDeviceFunction;
+  void* args[] = {const_cast<rtmi::FastParams*>(p), const_cast<rtmi::Aov32Params*>(q)};
+  (void)hipLaunchKernel(fn, dim3(blocks), dim3(256), args, shmem, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
+// Resident blocks per CU of the feature-buffer kernel; 0: none for the subset.
+extern "C" int rtmi_aov_f32_blocks_per_cu(unsigned subset, size_t shmem) {
+  return blocks_per_cu(aov_kernel(subset), 0, shmem);
+}
+
 extern "C" int rtmi_launch_shade_reduce32(const float* ray_rgb, long long ngroups, int group, float inv_len,
                                           float* rgb, void* stream) {
   const unsigned blocks = (unsigned)((ngroups + 255) / 256);

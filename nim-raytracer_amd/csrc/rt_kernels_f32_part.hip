@@ -7,6 +7,7 @@
 // without the sphere / box / rotation / point-light / reflection code paths
 // (fewer branches, fewer SALU, 66 instead of 72+ VGPRs).
 #include "rt_fast.h"
+#include "rt_fast_aov.h"
 #include "rt_fast_query.h"
 #include "rt_fast_shade.h"
 
@@ -37,6 +38,9 @@ constexpr bool has_shade(unsigned i) { return (i & 64u) == 0u; }
 // the float32 ray-query kernel depends on the geometry bits alone: it exists
 // for the 16 subsets of {sphere, box, mesh, general transform} (parts 0 and 1)
 constexpr bool has_trace(unsigned i) { return i < 16u; }
+// the feature-buffer kernel traces camera rays and shades nothing: it exists
+// for the same 16 subsets with and without stochastic sampling (parts 0, 1, 8, 9)
+constexpr bool has_aov(unsigned i) { return (i & 48u) == 0u; }
 
 // The host address of kernel (family, subset I), null where the family has
 // none for the subset. Taking an address instantiates the kernel.
@@ -60,6 +64,9 @@ const void* kernel_of(int family) {
       break;
     case rtmi::K32_TRACE:
       if constexpr (has_trace(I)) return (const void*)f::k_trace_rays_f32<F>;
+      break;
+    case rtmi::K32_AOV:
+      if constexpr (has_aov(I)) return (const void*)f::k_render_aov<F>;
       break;
   }
   return nullptr;

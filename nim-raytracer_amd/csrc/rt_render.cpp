@@ -225,7 +225,9 @@ struct Plan {
   int wave_bpc;
 };
 
-Plan plan_mapping(const rt_scene* s, const rt_options* o, const Mapping& mp, int spp) {
+// aov: the plan of a feature-buffer call (rt_render_aovs*) — the render's
+// lanes and tiles for these options, k_render_aov's subset and residency.
+Plan plan_mapping(const rt_scene* s, const rt_options* o, const Mapping& mp, int spp, bool aov = false) {
   Plan pl{};
   pl.sub = f32_subset(s, o);
   // a pixel's samples spread over up to 64 lanes
@@ -254,7 +256,12 @@ Plan plan_mapping(const rt_scene* s, const rt_options* o, const Mapping& mp, int
   pl.ngroups = (int)std::min<long long>(ng, INT32_MAX);
   const long long want = (ng + 3) / 4;
   // work-queue kernel: launch what is resident
-  pl.fast_bpc = rtmi_render_f32_blocks_per_cu((o->flags & RT_FLAG_COUNT_TRAVERSAL) ? 1 : 0, pl.sub, pl.shmem);
+  if (aov) {  // camera rays only: point lights and reflection cannot matter
+    pl.sub &= 15u | (unsigned)SUB_STOCHASTIC;
+    pl.fast_bpc = rtmi_aov_f32_blocks_per_cu(pl.sub, pl.shmem);
+  } else {
+    pl.fast_bpc = rtmi_render_f32_blocks_per_cu((o->flags & RT_FLAG_COUNT_TRAVERSAL) ? 1 : 0, pl.sub, pl.shmem);
+  }
   const long long cap = std::min<long long>(s->max_waves / 4, (long long)pl.fast_bpc * s->num_cus);
   pl.blocks = (int)std::max(1LL, std::min<long long>(want, cap));
   return pl;
@@ -674,6 +681,38 @@ void plan_kernels(const rt_scene* s, const rt_options* o, const Mapping& mp, con
   }
 }
 
+// The mapping words of FastParams: which pixels the launch covers (Mapping)
+// and how its pixel groups lie on the waves (the plan's lanes and tiles) —
+// what group_pixel reads. A render and a feature-buffer call fill them here.
+void mapping_words(const Mapping& mp, const Plan& pl, int spp, FastParams& p) {
+  p.mode = mp.mode;
+  p.y0 = mp.y0;
+  p.nrows = mp.nrows;
+  p.ncols = mp.ncols;
+  p.step = mp.step;
+  p.max_step = mp.max_step;
+  p.band_h = mp.band_h;
+  p.rank = mp.rank;
+  p.world = mp.world;
+  p.lanes_per_px = pl.L;
+  p.log2_lanes = pl.log2L;
+  p.tile_x = pl.tx;
+  p.tile_y = pl.ty;
+  p.log2_tile_x = 0;
+  while ((1 << p.log2_tile_x) < pl.tx) ++p.log2_tile_x;
+  p.inv_band_h = mp.band_h > 0 ? (float)(1.0 / (double)mp.band_h) : 0.0f;
+  p.tiles_x = pl.tiles_x;
+  p.ngroups = pl.ngroups;
+  p.iters = (spp + pl.L - 1) / pl.L;
+  {  // g / tiles_x by multiply-shift: m = floor(2^(31+s) / d) + 1, s = ceil(log2 d), exact for g < 2^31
+    const uint64_t d = (uint64_t)std::max(1, pl.tiles_x);
+    int sh = 0;
+    while ((1ull << sh) < d) ++sh;
+    p.tx_shift = 31 + sh;
+    p.tx_magic = (uint32_t)((1ull << (31 + sh)) / d + 1ull);
+  }
+}
+
 // The float32 launch's parameters and plan, and this call's camera-dependent
 // data built on the device (rt_frame.h) in stream order before the render
 // kernels: the mesh's camera-ray lists (>= 16 samples per pixel), the object
@@ -696,33 +735,8 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
   p.seed = o->seed;
   p.max_depth = o->max_ray_depth;
   p.flags = (int32_t)o->flags;
-  p.mode = mp.mode;
-  p.y0 = mp.y0;
-  p.nrows = mp.nrows;
-  p.ncols = mp.ncols;
-  p.step = mp.step;
-  p.max_step = mp.max_step;
-  p.band_h = mp.band_h;
-  p.rank = mp.rank;
-  p.world = mp.world;
   pl = plan_mapping(s, o, mp, spp);
-  p.lanes_per_px = pl.L;
-  p.log2_lanes = pl.log2L;
-  p.tile_x = pl.tx;
-  p.tile_y = pl.ty;
-  p.log2_tile_x = 0;
-  while ((1 << p.log2_tile_x) < pl.tx) ++p.log2_tile_x;
-  p.inv_band_h = mp.band_h > 0 ? (float)(1.0 / (double)mp.band_h) : 0.0f;
-  p.tiles_x = pl.tiles_x;
-  p.ngroups = pl.ngroups;
-  p.iters = (spp + pl.L - 1) / pl.L;
-  {  // g / tiles_x by multiply-shift: m = floor(2^(31+s) / d) + 1, s = ceil(log2 d), exact for g < 2^31
-    const uint64_t d = (uint64_t)std::max(1, pl.tiles_x);
-    int sh = 0;
-    while ((1ull << sh) < d) ++sh;
-    p.tx_shift = 31 + sh;
-    p.tx_magic = (uint32_t)((1ull << (31 + sh)) / d + 1ull);
-  }
+  mapping_words(mp, pl, spp, p);
   {  // the 32-bit wave counters stay in registers across work items and are
      // added to the 64-bit totals before any can wrap: per item at most
      // 64 lanes x iters samples x levels x (1 + lights) traces x objects hits
@@ -1287,6 +1301,181 @@ extern "C" int rt_render_bands_device(rt_scene* s, const rt_options* o, float* d
   std::lock_guard<std::mutex> lk(s->mu);
   DeviceGuard g(s->device);
   return render_device(s, o, mp, d_bands, (hipStream_t)stream, out);
+}
+
+// ---- feature buffers (rt_render_aovs*, rt_fast_aov.h) ------------------------
+namespace {
+
+constexpr int kAovChannels = 6;
+// element size and count per pixel of rt_aov_buffers' channels, in field order
+constexpr size_t kAovElems[kAovChannels] = {1, 1, 1, 1, 3, 3};
+
+// What both forms check before they take the scene's lock. oc: the options the
+// call goes by — bias, max_ray_depth and every flag but RT_FLAG_NO_BINNING are
+// not the caller's to matter. *empty: no rows, nothing to do.
+int aov_check(const rt_scene* s, const rt_options* o, const rt_aov_buffers* b, int32_t y0, int32_t y1, rt_options* oc,
+              Mapping* mp, bool* empty) {
+  if (!s || !o || !b) return fail(RT_E_INVALID, "null argument");
+  *oc = *o;
+  oc->bias = 0.0;
+  oc->max_ray_depth = 0;
+  oc->flags = o->flags & RT_FLAG_NO_BINNING;
+  if (int rc = check_options(s, oc)) return rc;
+  if (o->precision != RT_FP32)
+    return fail(RT_E_UNSUPPORTED, "rt_render_aovs renders the feature buffers of an RT_FP32 frame (precision %d)",
+                o->precision);
+  if (int rc = lines_mapping(oc, y0, y1, 1, 1, mp)) return rc;
+  *empty = mp->nrows == 0;
+  if (!*empty && !b->alpha && !b->depth && !b->object && !b->face && !b->normal && !b->albedo)
+    return fail(RT_E_INVALID, "no feature buffer requested: every channel is null");
+  return RT_OK;
+}
+
+// The device body (the scene's lock held, its device current): a render-class
+// call — ordered after the scene's calls in flight, on the scene's current
+// per-call buffer set, its Stats rows the scene's — that classifies nothing,
+// measures no launch order and consumes none. b's pointers are device memory.
+int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov_buffers& b, hipStream_t st,
+               rt_stats* out) {
+  s->stats_kept = true;
+  if (st != s->done_stream) HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
+  // in stream order on the last call's buffer set (no swap: a pipelined
+  // sequence of renders alternates as if this call were not there)
+  s->timed = false;
+  s->pipe = false;
+  s->fr.counted = false;
+  s->fr.listed = false;
+  s->fr.uniform = false;
+  s->fr.ground = false;
+  s->mesh1 = false;
+  s->pending_reduce = 0;
+  s->last_lean = 0;
+  s->last_lean_kind = 0;
+  s->last_general = 0;
+  s->last_batched = 0;
+  FastParams p;
+  std::memset(&p, 0, sizeof p);
+  // the scene words; no light or object grid is reachable from a camera ray
+  fast_scene_words(s, RT_FLAG_NO_BINNING, p);
+  p.partials = s->partials.p;
+  p.queue = s->queue.p;
+  fast_camera(s->c2w, s->fov, o, p);
+  p.seed = o->seed;
+  const Plan pl = plan_mapping(s, o, mp, p.spp, true);
+  if (pl.fast_bpc <= 0)
+    return fail(RT_E_DEVICE, "the feature-buffer kernel (subset %u) is not resident on this device", pl.sub);
+  mapping_words(mp, pl, p.spp, p);
+  s->last_general = p.ngroups;
+  // per item at most 64 lanes x iters samples x objects hits in one 32-bit counter
+  p.stat_flush = (int32_t)std::min<uint64_t>(
+      1u << 20, std::max<uint64_t>(1, 0xFFFFFFFFull / (64ull * (uint64_t)p.iters * (uint64_t)std::max(1, s->nobj))));
+  p.shards = std::min(kQueueShards, pl.blocks);
+  // the queue heads and the Stats accumulator behind them: one fill
+  unsigned int* const zero = s->queue.p;
+  const int nzero = (int)(rt_scene::kQueueWords + 2 * (size_t)kStatSlots);
+  bool zeroed = false;
+  // this call's face lists, pixel records and object masks, wherever an
+  // RT_FP32 render of these options builds them (plan_kernels' pl.build)
+  if (!(o->flags & RT_FLAG_NO_BINNING) && pl.L >= 16 && sampler_in_pixel(o->aa_kind)) {
+    bool lists = false, masks = false;
+    const bool records = pl.L == 64;
+    if (int rc = frame_build(s, o, mp, p, records, false, false, false, zero, nzero, st, &lists, &zeroed)) return rc;
+    if (lists) {
+      p.pix_slots = s->fr.slots.p;
+      p.pix_cnt = s->fr.info.p;
+      p.slot_lg = s->fr.slot_lg;
+      if (records) p.pix_info = s->fr.info.p;
+    }
+    if (s->objbins) {
+      if (int rc = frame_obj_masks(s, o, mp, st, &masks)) return rc;
+      if (masks) p.obj_pix = s->fr.omask.p;
+    }
+  }
+  if (!zeroed) HIP_TRY(hipMemsetAsync(zero, 0, (size_t)nzero * sizeof(unsigned int), st));
+  Aov32Params q;
+  q.alpha = b.alpha;
+  q.depth = b.depth;
+  q.object = b.object;
+  q.face = b.face;
+  q.normal = b.normal;
+  q.albedo = b.albedo;
+  q.obj_albedo = s->albedo32.p;
+  if (const int e = rtmi_launch_aov_f32(&p, &q, pl.sub, pl.blocks, pl.shmem, st))
+    return fail(RT_E_DEVICE, "feature-buffer kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  s->pending_reduce = pl.blocks * 4;
+  if (out)
+    if (int rc = flush_reduce(s, st)) return rc;
+  HIP_TRY(hipEventRecord(s->fr.used, st));
+  s->fr.used_rec = true;
+  s->done = s->fr.used;
+  s->done_stream = st;
+  if (out) return read_stats(s, st, out);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_render_aovs_device(rt_scene* s, const rt_options* o, const rt_aov_buffers* d_out, int32_t y0,
+                                     int32_t y1, void* stream, rt_stats* out) {
+  rt_options oc;
+  Mapping mp;
+  bool empty = false;
+  if (int rc = aov_check(s, o, d_out, y0, y1, &oc, &mp, &empty)) return rc;
+  if (empty) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  return aov_device(s, &oc, mp, *d_out, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_render_aovs(rt_scene* s, const rt_options* o, const rt_aov_buffers* out_bufs, int32_t y0, int32_t y1,
+                              rt_stats* out) {
+  rt_options oc;
+  Mapping mp;
+  bool empty = false;
+  if (int rc = aov_check(s, o, out_bufs, y0, y1, &oc, &mp, &empty)) return rc;
+  if (empty) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  // the wanted channels' device copies, each a whole frame (the kernel indexes
+  // by image pixel), 256-byte aligned; only rows [y0, y1) come back
+  void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
+                                    out_bufs->face,  out_bufs->normal, out_bufs->albedo};
+  const size_t npx = (size_t)o->width * (size_t)o->height;
+  size_t off[kAovChannels], total = 0;
+  for (int c = 0; c < kAovChannels; ++c) {
+    off[c] = total;
+    if (host[c]) total += (npx * kAovElems[c] * 4 + 255) & ~(size_t)255;
+  }
+  // (the staging buffer's last user was a host call, which waited for its copies)
+  if (s->aov_stage.n < total)
+    if (int rc = s->aov_stage.alloc(total)) return rc;
+  unsigned char* const base = s->aov_stage.p;
+  rt_aov_buffers d{};
+  d.alpha = host[0] ? (float*)(base + off[0]) : nullptr;
+  d.depth = host[1] ? (float*)(base + off[1]) : nullptr;
+  d.object = host[2] ? (int32_t*)(base + off[2]) : nullptr;
+  d.face = host[3] ? (int32_t*)(base + off[3]) : nullptr;
+  d.normal = host[4] ? (float*)(base + off[4]) : nullptr;
+  d.albedo = host[5] ? (float*)(base + off[5]) : nullptr;
+  hipStream_t st = s->stream;
+  if (int rc = aov_device(s, &oc, mp, d, st, nullptr)) return rc;
+  for (int c = 0; c < kAovChannels; ++c) {
+    if (!host[c]) continue;
+    const size_t row = (size_t)o->width * kAovElems[c] * 4;
+    HIP_TRY(hipMemcpyAsync((unsigned char*)host[c] + (size_t)y0 * row, base + off[c] + (size_t)y0 * row,
+                           (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost, st));
+  }
+  rt_stats local{};
+  if (int rc = flush_reduce(s, st)) return rc;
+  if (int rc = read_stats(s, st, &local)) return rc;  // (waits for the stream: the copies have landed)
+  if (out) *out = local;
+  return RT_OK;
 }
 
 extern "C" int rt_scene_last_stats(rt_scene* s, rt_stats* out) {

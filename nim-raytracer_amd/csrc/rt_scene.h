@@ -131,6 +131,12 @@ struct rt_scene {
   double c2w[16];
   double bg[3];
   FastData f32;
+  // (float)rt_object_desc.albedo of every object, nobj * 3: the feature-buffer
+  // kernel's albedo channel (rt_fast_aov.h); filled by rt_scene_create,
+  // refreshed by rt_scene_set_objects. aov_stage: rt_render_aovs' device
+  // copies of the wanted channels.
+  DevBuf<float> albedo32;
+  DevBuf<unsigned char> aov_stage;
   PrecisionData<double> f64;
   DevBuf<BvhNode> nodes;
   DevBuf<unsigned long long> partials;
@@ -297,7 +303,7 @@ struct rt_scene {
                bin_dev.bytes() + sat_dev.bytes() + objbox_dev.bytes() + lrec.bytes() + grec.bytes() + fr.bytes() +
                fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + q_shade.bytes() + q_shade32.bytes() +
                refit_parent.bytes() +
-               refit_arrivals.bytes() + mesh_scratch.bytes();
+               refit_arrivals.bytes() + mesh_scratch.bytes() + albedo32.bytes() + aov_stage.bytes();
     for (const MeshKeep& k : mesh_keep) b += k.verts.bytes() + k.faces.bytes() + k.order.bytes();
     for (const std::unique_ptr<Order>& o : orders) b += o->cost.bytes() + o->perm.bytes();
     return b;
@@ -379,6 +385,8 @@ template <class R>
 void fill_objects(const rt_object_desc* objs, int32_t n, std::vector<DevObject<R>>& out);
 void fill_fast_objects(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<float>>& dm,
                        std::vector<FObj>& fo, std::vector<FObjX>& fx);
+// (float)albedo[c] of every object, n * 3 (rt_scene::albedo32)
+void fill_albedo32(const rt_object_desc* objs, int32_t n, std::vector<float>& out);
 // the bin boxes (rt_bins.h ObjBox); dm: the meshes' boxes in float64 (calcAABB)
 void fill_obj_boxes(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<double>>& dm,
                     std::vector<ObjBox>& boxes);

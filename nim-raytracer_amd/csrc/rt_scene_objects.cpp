@@ -100,6 +100,12 @@ void fill_fast_objects(const rt_object_desc* objs, int32_t n, const std::vector<
   }
 }
 
+void fill_albedo32(const rt_object_desc* objs, int32_t n, std::vector<float>& out) {
+  out.resize((size_t)n * 3);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = (float)objs[i].albedo[k];
+}
+
 void fill_obj_boxes(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<double>>& dm,
                     std::vector<ObjBox>& boxes) {
   boxes.assign((size_t)n, ObjBox{});
@@ -151,6 +157,7 @@ struct ObjState {
   DevBuf<DevObject<double>> o64;
   DevBuf<FObj> fo;
   DevBuf<FObjX> fx;
+  DevBuf<float> albedo32;
   DevBuf<DevObjBox> objbox;
   std::vector<FObj> h_fo;
   std::vector<float> h_obj_ty;
@@ -191,7 +198,11 @@ extern "C" int rt_scene_set_objects(rt_scene* s, const rt_object_desc* objects, 
     fill_objects<double>(objects, num_objects, o64);
     fill_fast_objects(objects, num_objects, s->h_dm32, ns.h_fo, fx);
     for (const FObj& q : ns.h_fo) ns.h_obj_ty.push_back(q.t[1]);
-    if ((rc = ns.o64.upload(o64)) || (rc = ns.fo.upload(ns.h_fo)) || (rc = ns.fx.upload(fx))) return rc;
+    std::vector<float> alb;
+    fill_albedo32(objects, num_objects, alb);
+    if ((rc = ns.o64.upload(o64)) || (rc = ns.fo.upload(ns.h_fo)) || (rc = ns.fx.upload(fx)) ||
+        (rc = ns.albedo32.upload(alb)))
+      return rc;
   }
   fill_obj_meta(objects, num_objects, ns.meta);
   ns.desc.assign(objects, objects + num_objects);
@@ -234,6 +245,7 @@ extern "C" int rt_scene_set_objects(rt_scene* s, const rt_object_desc* objects, 
   std::swap(s->f64.objects, ns.o64);
   std::swap(s->f32.objs, ns.fo);
   std::swap(s->f32.objx, ns.fx);
+  std::swap(s->albedo32, ns.albedo32);
   if (s->objbins) std::swap(s->objbox_dev, ns.objbox);
   s->h_fo.swap(ns.h_fo);
   s->h_obj_ty.swap(ns.h_obj_ty);

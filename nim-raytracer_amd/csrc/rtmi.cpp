@@ -468,8 +468,10 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     s->h_fm = fm;
     s->h_fo = fo;
     int rc;
+    std::vector<float> alb;
+    fill_albedo32(d->objects, d->num_objects, alb);
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
-        (rc = s->f32.normals.upload(n)))
+        (rc = s->f32.normals.upload(n)) || (rc = s->albedo32.upload(alb)))
       return rc;
   }
   {

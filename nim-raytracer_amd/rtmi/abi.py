@@ -150,6 +150,17 @@ class rt_hit32(C.Structure):
     ]
 
 
+class rt_aov_buffers(C.Structure):
+    _fields_ = [
+        ("alpha", C.POINTER(C.c_float)),
+        ("depth", C.POINTER(C.c_float)),
+        ("object", C.POINTER(C.c_int32)),
+        ("face", C.POINTER(C.c_int32)),
+        ("normal", C.POINTER(C.c_float)),
+        ("albedo", C.POINTER(C.c_float)),
+    ]
+
+
 RT_QUEUE_STOPPED, RT_QUEUE_RUNNING, RT_QUEUE_SHUTDOWN = 0, 1, 2
 
 
@@ -273,6 +284,10 @@ SIGNATURES = {
                                             C.POINTER(rt_stats)]),
     "rt_pick_pixels_f32": (C.c_int, [_P, C.POINTER(rt_options), C.c_int64, C.POINTER(C.c_float), C.c_uint32,
                                      C.POINTER(rt_hit32), C.POINTER(C.c_float), C.POINTER(rt_stats)]),
+    "rt_render_aovs_device": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(rt_aov_buffers), C.c_int32, C.c_int32,
+                                        _P, C.POINTER(rt_stats)]),
+    "rt_render_aovs": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(rt_aov_buffers), C.c_int32, C.c_int32,
+                                 C.POINTER(rt_stats)]),
 }
 
 

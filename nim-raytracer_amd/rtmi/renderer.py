@@ -372,6 +372,66 @@ class DeviceScene:
             raise RuntimeError("rtmi_test_trace32_subset failed")
         return int(r)
 
+    # -- feature buffers (rt_render_aovs*) ------------------------------------
+    AOV_CHANNELS = ("alpha", "depth", "object", "face", "normal", "albedo")
+
+    def render_aovs(self, opts: Options, channels=AOV_CHANNELS, y0=0, y1=None, stream=None, stats=False,
+                    host=False, out=None):
+        """The per-pixel feature buffers of the fp32 frame `opts` describes,
+        rows [y0, y1): a dict by channel name — alpha, depth (height, width)
+        float32; object, face (height, width) int32; normal, albedo (height,
+        width, 3) float32 — over the frame's own samples (include/rtmi.h
+        rt_aov_buffers). CUDA torch tensors (the device form, enqueued on
+        `stream`; it waits only with stats=True), or numpy arrays with
+        host=True. Rows outside [y0, y1) are not written: they are zero in
+        arrays made here, and keep their contents in arrays passed in `out`
+        (a dict by channel name of contiguous arrays of those shapes and
+        types; numpy arrays select the host form). With stats=True returns
+        (dict, Stats)."""
+        w, h = int(opts.width), int(opts.height)
+        unknown = [c for c in channels if c not in self.AOV_CHANNELS]
+        if unknown:
+            raise ValueError(f"unknown feature buffers {unknown}: the channels are {self.AOV_CHANNELS}")
+        out = dict(out or {})
+        if any(_is_host(a) for a in out.values()):
+            host = True
+        bufs = abi.rt_aov_buffers()
+        res = {}
+        for c in self.AOV_CHANNELS:
+            if c not in channels:
+                continue
+            shape = (h, w, 3) if c in ("normal", "albedo") else (h, w)
+            ints = c in ("object", "face")
+            ctype = C.c_int32 if ints else C.c_float
+            a = out.get(c)
+            if host:
+                dt = np.int32 if ints else np.float32
+                if a is None:
+                    a = np.zeros(shape, dtype=dt)
+                elif not (_is_host(a) and a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == int(np.prod(shape))):
+                    raise ValueError(f"out[{c!r}] must be a contiguous {np.dtype(dt).name} numpy array of shape {shape}")
+                ptr = a.ctypes.data_as(C.POINTER(ctype))
+            else:
+                import torch
+                dt = torch.int32 if ints else torch.float32
+                if a is None:
+                    a = torch.zeros(shape, dtype=dt, device=f"cuda:{self.device}")
+                elif _is_host(a) or not (a.is_cuda and a.dtype == dt and a.is_contiguous()
+                                         and a.numel() == int(np.prod(shape))):
+                    raise ValueError(f"out[{c!r}] must be a contiguous {dt} CUDA/HIP tensor of shape {shape}")
+                ptr = C.cast(C.c_void_p(a.data_ptr()), C.POINTER(ctype))
+            setattr(bufs, c, ptr)
+            res[c] = a
+        o = opts.to_c()
+        st = abi.rt_stats()
+        pst = C.byref(st) if stats else None
+        y1 = h if y1 is None else int(y1)
+        if host:
+            check(lib().rt_render_aovs(self.h, C.byref(o), C.byref(bufs), int(y0), y1, pst))
+        else:
+            check(lib().rt_render_aovs_device(self.h, C.byref(o), C.byref(bufs), int(y0), y1, _stream(stream), pst))
+        return (res, Stats.from_c(st)) if stats else res
+
     def _query32_host(self, n, normals, stats, call):
         hits = np.zeros(n, dtype=_HIT32_DTYPE)
         nrm = np.zeros((n, 3), dtype=np.float32) if normals else None
