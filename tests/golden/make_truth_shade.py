@@ -6,7 +6,7 @@ subsets 35 and 63, which the oracle's camera cannot form):
 
 writes truth_shade_35.npz and truth_shade_63.npz: the rays, per ray the colour
 of truth._trace + truth.shade rounded to float64, its Counts, the primary
-hit's object and both margins. It refuses to write a fixture with more than
+hit's object, both margins and the float32 query margins. It refuses to write a fixture with more than
 2 % undecided rays, or one whose rays do not both hit and miss, or spawn no
 reflection rays."""
 import os

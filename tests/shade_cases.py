@@ -200,12 +200,13 @@ def truth_rays(bits, n=N_TRUTH):
 def truth_shade(bits, idx=None):
     """truth_shade_<bits>.npz (its rays idx): the rays, per ray the colour
     rounded to float64, the Counts (primary, tests, hits, shadow, reflection),
-    the primary hit's object and both margins."""
+    the primary hit's object, both margins and the float32 query margins
+    (truth.Margin.h32, n32: a radiance is decided at normal32)."""
     mp = truth._mp()
     orig, d = truth_rays(bits)
     idx = np.arange(len(orig)) if idx is None else np.asarray(idx)
     ts = truth.TruthScene(subset_scene(bits))
-    rgb, counts, obj, margin, margin32 = [], [], [], [], []
+    rgb, counts, obj, margin, margin32, hit32, normal32 = [], [], [], [], [], [], []
     for i in idx:
         st, mg = truth.Counts(), truth.Margin()
         o, dd = truth._vec(orig[i]), truth._vec(d[i])
@@ -219,6 +220,9 @@ def truth_shade(bits, idx=None):
         obj.append(ob)
         margin.append(mg.m)
         margin32.append(mg.m32)
+        hit32.append(mg.h32)
+        normal32.append(mg.n32)
     return {"orig": orig[idx], "dir": d[idx], "rgb": np.array(rgb, np.float64), "counts": np.array(counts, np.int64),
             "obj": np.array(obj, np.int32), "margin": np.array(margin, np.float64),
-            "margin32": np.array(margin32, np.float64)}
+            "margin32": np.array(margin32, np.float64), "hit32": np.array(hit32, np.float64),
+            "normal32": np.array(normal32, np.float64)}

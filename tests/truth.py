@@ -16,7 +16,12 @@ comparisons leave it out (the tests cap how many). The decisions:
 
   delta against 0 (sphere)                |delta| / max(b^2, |4ac|)
   |n.d| against 1e-6 (plane)              relative
-  tmin against tmax (slabs)               relative
+  tmin against tmax (slabs)               relative (a box of no thickness on
+                                          one axis, that slab binding both
+                                          ends: its t against the other slabs'
+                                          entries and exits; of no thickness
+                                          on two axes: 0, a hit needs the two
+                                          slabs' t equal)
   tmin against 0, t against 0             |t| |d| / (1 + |o|), object space
   det against 1e-6                        relative
   u against 0 and 1, v against 0,
@@ -39,6 +44,18 @@ choose because float32 resolves it, some hundred float32 roundings of a
 coordinate of 10); against EPS32 it would call every lit pixel undecided.
 The AABB's tmax *= 1.0000000000000004 is a float64 rounding guard: left out
 here, covered by EPS.
+
+The float32 QUERY margins (Margin.h32, n32; query(f32=True), pick(f32=True),
+and shade through the Margin it is handed) judge a float32 kernel on single
+rays. They are the float32 margin with the box normal's truncation taken
+apart. On the axis a box is hit on, v is 1.000001 by construction, a
+distance of 1e-6 that would call every box hit undecided against EPS32; a
+float32 kernel settles that axis by taking the dominant one when every axis
+truncates to 0, so the axis with the largest |v| is left out. The other two
+axes' distances to +-1 (a hit near an edge) decide the normal but not the
+hit: the hit margin h32 covers object, face, t and the Stats, the normal
+margin n32 is h32 and those two axes. A radiance is decided at n32 of its
+whole path.
 
 The fixture readers at the end (load, meta) need no mpmath."""
 import json
@@ -158,18 +175,31 @@ def _rel(a, b):
 
 class Margin:
     """Running minimum of the decisions' distances: m of all of them, m32 of
-    all but those add() is told to leave out of the float32 margin."""
-    __slots__ = ("m", "m32")
+    all but those add() is told to leave out of the float32 margin. h32 and
+    n32 are the float32 QUERY margins (module docstring): h32 of what m32
+    holds less the box normal's truncation (q32 = False), n32 of h32 and the
+    truncation's edge axes (add_edge)."""
+    __slots__ = ("m", "m32", "h32", "_e32")
 
     def __init__(self):
-        self.m = self.m32 = 1.0
+        self.m = self.m32 = self.h32 = self._e32 = 1.0
 
-    def add(self, d, f32=True):
+    def add(self, d, f32=True, q32=True):
         d = float(d)
         if d < self.m:
             self.m = d
         if f32 and d < self.m32:
             self.m32 = d
+        if f32 and q32 and d < self.h32:
+            self.h32 = d
+
+    def add_edge(self, d):
+        """A decision of the normal alone: in n32, in no other minimum."""
+        self._e32 = min(self._e32, float(d))
+
+    @property
+    def n32(self):
+        return min(self.h32, self._e32)
 
 
 def _t_margin(t, o, d):
@@ -227,6 +257,7 @@ def plane_intersect(o, d, mg):
 def aabb_intersect(vmin, vmax, o, d, mg):
     """Row a4: tmin, or None where the reference returns -inf."""
     tmin = tmax = None
+    slabs = []
     for i in range(3):
         if d[i] == 0:                       # invDir = +-inf
             if o[i] == vmin[i] or o[i] == vmax[i]:
@@ -242,6 +273,19 @@ def aabb_intersect(vmin, vmax, o, d, mg):
             t0, t1 = t1, t0
         tmin = t0 if tmin is None or t0 > tmin else tmin
         tmax = t1 if tmax is None or t1 < tmax else tmax
+        slabs.append((i, t0, t1))
+    flat = [s for s in slabs if vmin[s[0]] == vmax[s[0]] and s[1] == tmin and s[2] == tmax]
+    if flat:
+        # a slab of no thickness binds both ends: its entry and its exit are
+        # one number in any arithmetic, so tmin <= tmax rests on the other
+        # slabs' entries staying below it and their exits above it
+        # (tmin == tmax here, so the box is hit; a second flat slab binds at
+        # the same t and adds _rel(tk, tk) = 0)
+        k, tk = flat[0][0], flat[0][1]
+        for i, t0, t1 in slabs:
+            if i != k:
+                mg.add(min(_rel(t0, tk), _rel(tk, t1)))
+        return tmin
     mg.add(_rel(tmin, tmax))
     return tmin if tmin <= tmax else None
 
@@ -453,24 +497,31 @@ def hit_normal(ts, obj, face, hit_w, mg=None):
             n = _normalize(h)
         else:
             bias = mp.mpf(1.000001)
-            n = []
+            n, vs = [], []
             for i in range(3):
                 c = (rec["vmin"][i] + rec["vmax"][i]) / 2
                 half = abs((rec["vmin"][i] - rec["vmax"][i]) / 2)
                 v = (h[i] - c) / half * bias
-                mg.add(abs(float(abs(v) - 1)))
+                mg.add(abs(float(abs(v) - 1)), q32=False)
+                vs.append(v)
                 n.append(mp.mpf(int(v)))    # truncation
+            hit_axis = max(range(3), key=lambda i: abs(vs[i]))
+            for i in range(3):              # the query margin: the hit axis is the dominant one
+                if i != hit_axis:
+                    mg.add_edge(abs(float(abs(vs[i]) - 1)))
             if not any(n):
-                mg.add(0.0)
+                mg.add(0.0, q32=False)
+                mg.add_edge(0.0)
                 return (mp.nan, mp.nan, mp.nan)
             n = _normalize(tuple(n))
     return xf_dir(rec["o2w"], n)
 
 
-def query(ts, orig, d, t_near=INF):
+def query(ts, orig, d, t_near=INF, f32=False):
     """What rt_trace_rays answers for one ray given in doubles (mpf triples
     are taken as they are): (obj, face, t, normal (3,), tests, hits, margin),
-    t and the normal rounded to float64; a miss has t = t_near, normal 0."""
+    t and the normal rounded to float64; a miss has t = t_near, normal 0.
+    f32: the float32 query margins (hit, normal) follow the margin."""
     mp = _mp()
     ts = _scene(ts)
     mg = Margin()
@@ -481,16 +532,16 @@ def query(ts, orig, d, t_near=INF):
     if obj >= 0:
         hit_w = tuple(o[i] + dd[i] * t for i in range(3))
         n = np.array([float(x) for x in hit_normal(ts, obj, face, hit_w, mg)])
-    return obj, face, float(t), n, tests, hits, mg.m
+    return (obj, face, float(t), n, tests, hits, mg.m) + ((mg.h32, mg.n32) if f32 else ())
 
 
-def pick(ts, w, h, x, y):
+def pick(ts, w, h, x, y, f32=False):
     """rt_pick_pixels: castPrimaryRay through the scene's camera (unrounded),
     traced with t_near = +inf. Returns (orig (3,), dir (3,)) + query()'s tuple."""
     ts = _scene(ts)
     o, d = cast_primary_ray(w, h, x, y, ts.fov, ts.c2w)
     f = lambda v: np.array([float(c) for c in v])
-    return (f(o), f(d)) + query(ts, o, d)
+    return (f(o), f(d)) + query(ts, o, d, f32=f32)
 
 
 # ---- a12-a15: shade, pixel -------------------------------------------------------------
