@@ -968,6 +968,54 @@ int rt_render_aovs_device(rt_scene *scene, const rt_options *opts, const rt_aov_
 int rt_render_aovs(rt_scene *scene, const rt_options *opts, const rt_aov_buffers *out_bufs,
                    int32_t y0, int32_t y1, rt_stats *out);
 
+/* Float64 feature buffers: the same channels of an RT_FP64 frame, in float64
+ * and with no tolerance anywhere — every channel of every pixel has exactly
+ * one correct bit pattern.
+ *
+ * Pixel (x, y) of rows [y0, y1), sample s, is the RT_FP64 render's for the
+ * same width, height, aa_kind, grid_size and seed: akNone at (x, y); akGrid
+ * sample s = sj*m + si at x + (si * (1.0/m) + (1.0/m) * 0.5), likewise y, each
+ * operation rounded to float64; the stochastic kinds at x + sx[s], y + sy[s]
+ * of the pixel's sample table. Its ray is castPrimaryRay's as the RT_FP64
+ * render forms it, its hit what rt_pick_pixels returns at that position, bit
+ * for bit: t, obj, face and normal. inv_len is 1.0 / (double)spp.
+ *  - normal and albedo start from +0.0, add the value of every hitting sample
+ *    in sample-index order s = 0 .. spp-1 (calcPixel's order, renderer.nim:
+ *    147-159), and are multiplied once by inv_len. The order is fixed, so the
+ *    bytes do not depend on the flags, on how samples lie on the device's
+ *    lanes or on the size of this call's per-pixel face lists.
+ *  - opts: width, height, aa_kind, grid_size, seed, precision and flags are
+ *    read; bias and max_ray_depth are not. precision must be RT_FP64 (RT_FP32
+ *    is RT_E_INVALID: rt_render_aovs is that call); the sampler limits are an
+ *    RT_FP64 render's. Of flags RT_FLAG_NO_BINNING (the camera rays search
+ *    the BVH: no per-pixel lists or skip records) and RT_FLAG_F64_PER_LANE
+ *    (one lane per pixel also where akGrid with >= 64 samples would take one
+ *    pixel per wave) are honoured; every channel and the Stats are
+ *    byte-identical with either set. Other bits are ignored.
+ *  - Rows outside [y0, y1) and NULL channels are never written. A pixel none
+ *    of whose samples hits gets alpha 0, depth +inf, ids -1 and sums +0.
+ *  - out (may be NULL): as rt_render_aovs, num_intersection_hits being
+ *    rt_pick_pixels' over the same positions. A _device call with out == NULL
+ *    only enqueues work on hip_stream.
+ *  - The call class and the RT_E_INVALID cases are rt_render_aovs': a
+ *    render-class call that leaves the next colour render of either precision
+ *    its bytes, Stats and diagnostics. */
+typedef struct rt_aov_buffers64 {
+  double  *alpha;   /* (double)hits * inv_len */
+  double  *depth;   /* smallest tHit over the pixel's samples; +inf when none hits */
+  int32_t *object;  /* rt_hit.obj of the sample with the smallest (tHit, sample index); -1 */
+  int32_t *face;    /* rt_hit.face of that sample; -1 */
+  double  *normal;  /* x3: the ordered sum of the hitNormal rt_pick_pixels returns (not
+                       renormalised), times inv_len */
+  double  *albedo;  /* x3: the ordered sum of rt_object_desc.albedo[c] of the hit object as
+                       given, times inv_len */
+} rt_aov_buffers64;
+
+int rt_render_aovs_f64_device(rt_scene *scene, const rt_options *opts, const rt_aov_buffers64 *d_out,
+                              int32_t y0, int32_t y1, void *hip_stream, rt_stats *out);
+int rt_render_aovs_f64(rt_scene *scene, const rt_options *opts, const rt_aov_buffers64 *out_bufs,
+                       int32_t y0, int32_t y1, rt_stats *out);
+
 /* ---- helpers ----------------------------------------------------------- */
 
 /* glm-style inverse of a column-major 4x4 (what geom.nim's

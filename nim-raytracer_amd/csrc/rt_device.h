@@ -736,6 +736,38 @@ __device__ __forceinline__ V3<R> object_normal(const RT_CONST DevObject<R>& ob, 
   return V3<R>{R(0), R(0), R(0)};
 }
 
+// hitNormal (renderer.nim:83-88) of the float64 queries and feature buffers
+// (k_trace_rays, rt_kernels_aov64.hip): the world-space normal at the hit h
+// of the ray (o, d) for the lanes with `lit`, +0 for the others, gathered per
+// distinct object hit by the wave so the object record is read with scalar
+// loads. Not renormalised. Wave-uniform control flow only.
+__device__ __forceinline__ V3<double> hit_normal(const RT_CONST RenderParams<double>& p, V3<double> o, V3<double> d,
+                                                 const Hit<double>& h, bool lit) {
+  using R = double;
+  const V3<R> hw{o.x + d.x * h.t, o.y + d.y * h.t, o.z + d.z * h.t};
+  V3<R> N{R(0), R(0), R(0)};
+  unsigned long long pending = ballot(lit);
+  while (pending) {
+    const int lead = (int)__builtin_ctzll(pending);
+    const int oi = __builtin_amdgcn_readlane(h.obj, lead);
+    const bool mine = lit && h.obj == oi;
+    pending &= ~ballot(mine);
+    const RT_CONST DevObject<R>& ob = cptr(p.objects)[oi];
+    if (mine) {
+      V3<R> nrm;
+      if (h.tri >= 0) {
+        const R* fn = p.normals + 3 * (size_t)(cptr(p.meshes)[ob.mesh].normal_base + h.tri);
+        nrm = V3<R>{fn[0], fn[1], fn[2]};
+      } else {
+        const V3<R> ho = xform_xf<R, true>(ob.xf, ob.w2o, hw);
+        nrm = object_normal<R>(ob, ob.type, ho);
+      }
+      N = xform_xf<R, false>(ob.xf, ob.o2w, nrm);
+    }
+  }
+  return N;
+}
+
 // One camera sample: trace + shade with the reflection recursion unrolled
 // into a loop of levels. Returns the sample colour (renderer.nim:71-127).
 // LEVELS: the reflection levels compiled in (1: a scene without reflective

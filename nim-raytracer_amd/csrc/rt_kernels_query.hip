@@ -50,29 +50,8 @@ __global__ __launch_bounds__(256) void k_trace_rays(const RenderParams<double> p
     const Hit<R> h = trace<R, false>(p, o, d, tn, ok, shadow, ws);
     const bool lit = ok && h.obj >= 0;
     if (q.normals) {
-      // hitNormal (renderer.nim:83-88), gathered per distinct object hit by
-      // the wave so the object record is read with scalar loads
-      const V3<R> hw{o.x + d.x * h.t, o.y + d.y * h.t, o.z + d.z * h.t};
-      V3<R> N{R(0), R(0), R(0)};
-      unsigned long long pending = ballot(lit);
-      while (pending) {
-        const int lead = (int)__builtin_ctzll(pending);
-        const int oi = __builtin_amdgcn_readlane(h.obj, lead);
-        const bool mine = lit && h.obj == oi;
-        pending &= ~ballot(mine);
-        const RT_CONST DevObject<R>& ob = cptr(p.objects)[oi];
-        if (mine) {
-          V3<R> nrm;
-          if (h.tri >= 0) {
-            const R* fn = p.normals + 3 * (size_t)(cptr(p.meshes)[ob.mesh].normal_base + h.tri);
-            nrm = V3<R>{fn[0], fn[1], fn[2]};
-          } else {
-            const V3<R> ho = xform_xf<R, true>(ob.xf, ob.w2o, hw);
-            nrm = object_normal<R>(ob, ob.type, ho);
-          }
-          N = xform_xf<R, false>(ob.xf, ob.o2w, nrm);
-        }
-      }
+      // hitNormal (renderer.nim:83-88): rt_device.h hit_normal
+      const V3<R> N = hit_normal(p, o, d, h, lit);
       if (in) {
         R* out = q.normals + 3 * i;
         out[0] = N.x; out[1] = N.y; out[2] = N.z;

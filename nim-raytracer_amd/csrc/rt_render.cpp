@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "rt_aov64.h"
+#include "rt_aov_stage.h"
 #include "rt_scene.h"
 
 namespace rtmi {
@@ -1306,9 +1308,15 @@ extern "C" int rt_render_bands_device(rt_scene* s, const rt_options* o, float* d
 // ---- feature buffers (rt_render_aovs*, rt_fast_aov.h) ------------------------
 namespace {
 
-constexpr int kAovChannels = 6;
-// element size and count per pixel of rt_aov_buffers' channels, in field order
-constexpr size_t kAovElems[kAovChannels] = {1, 1, 1, 1, 3, 3};
+// The rows of a feature-buffer call in either precision: one image row per
+// mapping row. *empty: no rows, nothing to do; otherwise a channel must be
+// wanted (any).
+int aov_rows(const rt_options* oc, int32_t y0, int32_t y1, bool any, Mapping* mp, bool* empty) {
+  if (int rc = lines_mapping(oc, y0, y1, 1, 1, mp)) return rc;
+  *empty = mp->nrows == 0;
+  if (!*empty && !any) return fail(RT_E_INVALID, "no feature buffer requested: every channel is null");
+  return RT_OK;
+}
 
 // What both forms check before they take the scene's lock. oc: the options the
 // call goes by — bias, max_ray_depth and every flag but RT_FLAG_NO_BINNING are
@@ -1324,19 +1332,15 @@ int aov_check(const rt_scene* s, const rt_options* o, const rt_aov_buffers* b, i
   if (o->precision != RT_FP32)
     return fail(RT_E_UNSUPPORTED, "rt_render_aovs renders the feature buffers of an RT_FP32 frame (precision %d)",
                 o->precision);
-  if (int rc = lines_mapping(oc, y0, y1, 1, 1, mp)) return rc;
-  *empty = mp->nrows == 0;
-  if (!*empty && !b->alpha && !b->depth && !b->object && !b->face && !b->normal && !b->albedo)
-    return fail(RT_E_INVALID, "no feature buffer requested: every channel is null");
-  return RT_OK;
+  return aov_rows(oc, y0, y1, b->alpha || b->depth || b->object || b->face || b->normal || b->albedo, mp, empty);
 }
 
-// The device body (the scene's lock held, its device current): a render-class
-// call — ordered after the scene's calls in flight, on the scene's current
-// per-call buffer set, its Stats rows the scene's — that classifies nothing,
-// measures no launch order and consumes none. b's pointers are device memory.
-int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov_buffers& b, hipStream_t st,
-               rt_stats* out) {
+// How a feature-buffer call of either precision enters the scene (its lock
+// held, its device current): a render-class call — ordered after the scene's
+// calls in flight, on the scene's current per-call buffer set, its Stats rows
+// the scene's — that classifies nothing, measures no launch order and
+// consumes none.
+int aov_begin(rt_scene* s, hipStream_t st) {
   s->stats_kept = true;
   if (st != s->done_stream) HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
   // in stream order on the last call's buffer set (no swap: a pipelined
@@ -1353,6 +1357,26 @@ int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov
   s->last_lean_kind = 0;
   s->last_general = 0;
   s->last_batched = 0;
+  return RT_OK;
+}
+
+// ... and leaves it: `blocks` blocks of four waves left their Stats rows.
+int aov_end(rt_scene* s, hipStream_t st, int blocks, rt_stats* out) {
+  s->pending_reduce = blocks * 4;
+  if (out)
+    if (int rc = flush_reduce(s, st)) return rc;
+  HIP_TRY(hipEventRecord(s->fr.used, st));
+  s->fr.used_rec = true;
+  s->done = s->fr.used;
+  s->done_stream = st;
+  if (out) return read_stats(s, st, out);
+  return RT_OK;
+}
+
+// The float32 device body. b's pointers are device memory.
+int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov_buffers& b, hipStream_t st,
+               rt_stats* out) {
+  if (int rc = aov_begin(s, st)) return rc;
   FastParams p;
   std::memset(&p, 0, sizeof p);
   // the scene words; no light or object grid is reachable from a camera ray
@@ -1402,18 +1426,156 @@ int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov
   q.obj_albedo = s->albedo32.p;
   if (const int e = rtmi_launch_aov_f32(&p, &q, pl.sub, pl.blocks, pl.shmem, st))
     return fail(RT_E_DEVICE, "feature-buffer kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-  s->pending_reduce = pl.blocks * 4;
-  if (out)
-    if (int rc = flush_reduce(s, st)) return rc;
-  HIP_TRY(hipEventRecord(s->fr.used, st));
-  s->fr.used_rec = true;
-  s->done = s->fr.used;
-  s->done_stream = st;
-  if (out) return read_stats(s, st, out);
+  return aov_end(s, st, pl.blocks, out);
+}
+
+// The scene's staging buffer sized for the wanted channels of a host form
+// (rt_aov_stage.h): off[c] from *base.
+int aov_stage(rt_scene* s, const void* const host[kAovChannels], const size_t px_bytes[kAovChannels],
+              const rt_options* o, size_t off[kAovChannels], unsigned char** base) {
+  const size_t total = aov_stage_offsets(host, px_bytes, (size_t)o->width * (size_t)o->height, off);
+  // (the staging buffer's last user was a host call, which waited for its copies)
+  if (s->aov_stage.n < total)
+    if (int rc = s->aov_stage.alloc(total)) return rc;
+  *base = s->aov_stage.p;
   return RT_OK;
 }
 
+// Rows [y0, y1) of the staged channels back to the caller, then the call's
+// Stats (which waits for the stream: the copies have landed).
+int aov_unstage(rt_scene* s, void* const host[kAovChannels], const size_t px_bytes[kAovChannels], const rt_options* o,
+                const size_t off[kAovChannels], int32_t y0, int32_t y1, hipStream_t st, rt_stats* out) {
+  for (int c = 0; c < kAovChannels; ++c) {
+    if (!host[c]) continue;
+    size_t begin, count;
+    aov_stage_rows(px_bytes[c], o->width, y0, y1, &begin, &count);
+    HIP_TRY(hipMemcpyAsync((unsigned char*)host[c] + begin, s->aov_stage.p + off[c] + begin, count,
+                           hipMemcpyDeviceToHost, st));
+  }
+  rt_stats local{};
+  if (int rc = flush_reduce(s, st)) return rc;
+  if (int rc = read_stats(s, st, &local)) return rc;
+  if (out) *out = local;
+  return RT_OK;
+}
+
+// ---- float64 feature buffers (rt_render_aovs_f64*, rt_kernels_aov64.hip) ------
+
+// aov_check's float64 twin. oc: bias and max_ray_depth are not the caller's
+// to matter, of the flags RT_FLAG_NO_BINNING and RT_FLAG_F64_PER_LANE are.
+int aov64_check(const rt_scene* s, const rt_options* o, const rt_aov_buffers64* b, int32_t y0, int32_t y1,
+                rt_options* oc, Mapping* mp, bool* empty) {
+  if (!s || !o || !b) return fail(RT_E_INVALID, "null argument");
+  if (o->precision == RT_FP32)
+    return fail(RT_E_INVALID, "rt_render_aovs_f64 renders the feature buffers of an RT_FP64 frame: "
+                              "rt_render_aovs is the RT_FP32 call");
+  *oc = *o;
+  oc->bias = 0.0;
+  oc->max_ray_depth = 0;
+  oc->flags = o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_F64_PER_LANE);
+  if (int rc = check_options(s, oc)) return rc;
+  return aov_rows(oc, y0, y1, b->alpha || b->depth || b->object || b->face || b->normal || b->albedo, mp, empty);
+}
+
+// The float64 device body: launch_f64's preparation for camera rays alone —
+// the parameters, the stochastic samplers' table scratch, this call's pixel
+// records and face lists under the render's conditions, the one-pixel-per-wave
+// grid — and no light-grid shadow records: no shadow ray is traced.
+int aov64_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov_buffers64& b, hipStream_t st,
+                 rt_stats* out) {
+  if (int rc = aov_begin(s, st)) return rc;
+  RenderParams<double> p;
+  int blocks = 1;
+  fill_params<double>(s, s->f64, o, mp, nullptr, p, &blocks);
+  s->last_general = p.ngroups;
+  if (p.aa_kind >= RT_AA_JITTERED) {
+    const size_t need = (size_t)blocks * 256 * 2 * (size_t)p.spp;
+    if (s->f64_tables.n < need) {
+      HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffer
+      if (int rc = s->f64_tables.alloc(need)) return rc;
+    }
+    p.sample_scratch = s->f64_tables.p;
+  }
+  bool lists = false;
+  if (!(o->flags & RT_FLAG_NO_BINNING) && sampler_in_pixel(o->aa_kind) && s->skippable) {
+    FastParams pf;
+    std::memset(&pf, 0, sizeof pf);
+    bool zeroed = false;
+    if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
+    if (lists) p.pix_info = s->fr.info.p;
+  }
+  // launch_f64's condition for k_render_px64
+  const int px = o->aa_kind == RT_AA_GRID && p.spp >= 64 && !(o->flags & RT_FLAG_F64_PER_LANE) ? 1 : 0;
+  if (px) {
+    if (lists) {
+      p.pix_slots = s->fr.slots.p;
+      p.slot_lg = s->fr.slot_lg;
+    }
+    p.tri_rec0 = (int32_t)s->num_nodes;
+    const long long nbatch = ((long long)mp.nrows * mp.ncols + rtmi_aov64_batch() - 1) / rtmi_aov64_batch();
+    const long long resident = (long long)std::max(1, rtmi_aov64_blocks_per_cu()) * s->num_cus;
+    blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
+  }
+  // the Stats accumulator (behind the queue heads, which no float64 kernel reads)
+  HIP_TRY(hipMemsetAsync(s->queue.p + rt_scene::kQueueWords, 0, 2 * (size_t)kStatSlots * sizeof(unsigned int), st));
+  Aov64Params q;
+  q.alpha = b.alpha;
+  q.depth = b.depth;
+  q.object = b.object;
+  q.face = b.face;
+  q.normal = b.normal;
+  q.albedo = b.albedo;
+  q.obj_albedo = s->albedo64.p;
+  if (const int e = rtmi_launch_aov_f64(&p, &q, px, blocks, st))
+    return fail(RT_E_DEVICE, "feature-buffer kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return aov_end(s, st, blocks, out);
+}
+
 }  // namespace
+
+extern "C" int rt_render_aovs_f64_device(rt_scene* s, const rt_options* o, const rt_aov_buffers64* d_out, int32_t y0,
+                                         int32_t y1, void* stream, rt_stats* out) {
+  rt_options oc;
+  Mapping mp;
+  bool empty = false;
+  if (int rc = aov64_check(s, o, d_out, y0, y1, &oc, &mp, &empty)) return rc;
+  if (empty) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  return aov64_device(s, &oc, mp, *d_out, (hipStream_t)stream, out);
+}
+
+extern "C" int rt_render_aovs_f64(rt_scene* s, const rt_options* o, const rt_aov_buffers64* out_bufs, int32_t y0,
+                                  int32_t y1, rt_stats* out) {
+  rt_options oc;
+  Mapping mp;
+  bool empty = false;
+  if (int rc = aov64_check(s, o, out_bufs, y0, y1, &oc, &mp, &empty)) return rc;
+  if (empty) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
+                                    out_bufs->face,  out_bufs->normal, out_bufs->albedo};
+  size_t off[kAovChannels];
+  unsigned char* base = nullptr;
+  if (int rc = aov_stage(s, host, kAovPxBytes64, o, off, &base)) return rc;
+  rt_aov_buffers64 d{};
+  d.alpha = host[0] ? (double*)(base + off[0]) : nullptr;
+  d.depth = host[1] ? (double*)(base + off[1]) : nullptr;
+  d.object = host[2] ? (int32_t*)(base + off[2]) : nullptr;
+  d.face = host[3] ? (int32_t*)(base + off[3]) : nullptr;
+  d.normal = host[4] ? (double*)(base + off[4]) : nullptr;
+  d.albedo = host[5] ? (double*)(base + off[5]) : nullptr;
+  hipStream_t st = s->stream;
+  if (int rc = aov64_device(s, &oc, mp, d, st, nullptr)) return rc;
+  return aov_unstage(s, host, kAovPxBytes64, o, off, y0, y1, st, out);
+}
 
 extern "C" int rt_render_aovs_device(rt_scene* s, const rt_options* o, const rt_aov_buffers* d_out, int32_t y0,
                                      int32_t y1, void* stream, rt_stats* out) {
@@ -1442,20 +1604,12 @@ extern "C" int rt_render_aovs(rt_scene* s, const rt_options* o, const rt_aov_buf
   }
   std::lock_guard<std::mutex> lk(s->mu);
   DeviceGuard g(s->device);
-  // the wanted channels' device copies, each a whole frame (the kernel indexes
-  // by image pixel), 256-byte aligned; only rows [y0, y1) come back
+  // the wanted channels' device copies (rt_aov_stage.h); only rows [y0, y1) come back
   void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
                                     out_bufs->face,  out_bufs->normal, out_bufs->albedo};
-  const size_t npx = (size_t)o->width * (size_t)o->height;
-  size_t off[kAovChannels], total = 0;
-  for (int c = 0; c < kAovChannels; ++c) {
-    off[c] = total;
-    if (host[c]) total += (npx * kAovElems[c] * 4 + 255) & ~(size_t)255;
-  }
-  // (the staging buffer's last user was a host call, which waited for its copies)
-  if (s->aov_stage.n < total)
-    if (int rc = s->aov_stage.alloc(total)) return rc;
-  unsigned char* const base = s->aov_stage.p;
+  size_t off[kAovChannels];
+  unsigned char* base = nullptr;
+  if (int rc = aov_stage(s, host, kAovPxBytes32, o, off, &base)) return rc;
   rt_aov_buffers d{};
   d.alpha = host[0] ? (float*)(base + off[0]) : nullptr;
   d.depth = host[1] ? (float*)(base + off[1]) : nullptr;
@@ -1465,17 +1619,7 @@ extern "C" int rt_render_aovs(rt_scene* s, const rt_options* o, const rt_aov_buf
   d.albedo = host[5] ? (float*)(base + off[5]) : nullptr;
   hipStream_t st = s->stream;
   if (int rc = aov_device(s, &oc, mp, d, st, nullptr)) return rc;
-  for (int c = 0; c < kAovChannels; ++c) {
-    if (!host[c]) continue;
-    const size_t row = (size_t)o->width * kAovElems[c] * 4;
-    HIP_TRY(hipMemcpyAsync((unsigned char*)host[c] + (size_t)y0 * row, base + off[c] + (size_t)y0 * row,
-                           (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost, st));
-  }
-  rt_stats local{};
-  if (int rc = flush_reduce(s, st)) return rc;
-  if (int rc = read_stats(s, st, &local)) return rc;  // (waits for the stream: the copies have landed)
-  if (out) *out = local;
-  return RT_OK;
+  return aov_unstage(s, host, kAovPxBytes32, o, off, y0, y1, st, out);
 }
 
 extern "C" int rt_scene_last_stats(rt_scene* s, rt_stats* out) {

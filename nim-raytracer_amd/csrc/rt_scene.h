@@ -137,6 +137,10 @@ struct rt_scene {
   // copies of the wanted channels.
   DevBuf<float> albedo32;
   DevBuf<unsigned char> aov_stage;
+  // rt_object_desc.albedo of every object as given, nobj * 3: the float64
+  // feature-buffer kernels' albedo channel (rt_kernels_aov64.hip; DevObject's
+  // albp is already divided by PI); filled and refreshed as albedo32 is
+  DevBuf<double> albedo64;
   PrecisionData<double> f64;
   DevBuf<BvhNode> nodes;
   DevBuf<unsigned long long> partials;
@@ -303,7 +307,7 @@ struct rt_scene {
                bin_dev.bytes() + sat_dev.bytes() + objbox_dev.bytes() + lrec.bytes() + grec.bytes() + fr.bytes() +
                fr2.bytes() + q_partials.bytes() + q_sort.bytes() + q_stage.bytes() + q_shade.bytes() + q_shade32.bytes() +
                refit_parent.bytes() +
-               refit_arrivals.bytes() + mesh_scratch.bytes() + albedo32.bytes() + aov_stage.bytes();
+               refit_arrivals.bytes() + mesh_scratch.bytes() + albedo32.bytes() + aov_stage.bytes() + albedo64.bytes();
     for (const MeshKeep& k : mesh_keep) b += k.verts.bytes() + k.faces.bytes() + k.order.bytes();
     for (const std::unique_ptr<Order>& o : orders) b += o->cost.bytes() + o->perm.bytes();
     return b;
@@ -387,6 +391,8 @@ void fill_fast_objects(const rt_object_desc* objs, int32_t n, const std::vector<
                        std::vector<FObj>& fo, std::vector<FObjX>& fx);
 // (float)albedo[c] of every object, n * 3 (rt_scene::albedo32)
 void fill_albedo32(const rt_object_desc* objs, int32_t n, std::vector<float>& out);
+// albedo[c] of every object as given, n * 3 (rt_scene::albedo64)
+void fill_albedo64(const rt_object_desc* objs, int32_t n, std::vector<double>& out);
 // the bin boxes (rt_bins.h ObjBox); dm: the meshes' boxes in float64 (calcAABB)
 void fill_obj_boxes(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<double>>& dm,
                     std::vector<ObjBox>& boxes);

@@ -106,6 +106,12 @@ void fill_albedo32(const rt_object_desc* objs, int32_t n, std::vector<float>& ou
     for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = (float)objs[i].albedo[k];
 }
 
+void fill_albedo64(const rt_object_desc* objs, int32_t n, std::vector<double>& out) {
+  out.resize((size_t)n * 3);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = objs[i].albedo[k];
+}
+
 void fill_obj_boxes(const rt_object_desc* objs, int32_t n, const std::vector<DevMesh<double>>& dm,
                     std::vector<ObjBox>& boxes) {
   boxes.assign((size_t)n, ObjBox{});
@@ -158,6 +164,7 @@ struct ObjState {
   DevBuf<FObj> fo;
   DevBuf<FObjX> fx;
   DevBuf<float> albedo32;
+  DevBuf<double> albedo64;
   DevBuf<DevObjBox> objbox;
   std::vector<FObj> h_fo;
   std::vector<float> h_obj_ty;
@@ -200,8 +207,10 @@ extern "C" int rt_scene_set_objects(rt_scene* s, const rt_object_desc* objects, 
     for (const FObj& q : ns.h_fo) ns.h_obj_ty.push_back(q.t[1]);
     std::vector<float> alb;
     fill_albedo32(objects, num_objects, alb);
+    std::vector<double> alb64;
+    fill_albedo64(objects, num_objects, alb64);
     if ((rc = ns.o64.upload(o64)) || (rc = ns.fo.upload(ns.h_fo)) || (rc = ns.fx.upload(fx)) ||
-        (rc = ns.albedo32.upload(alb)))
+        (rc = ns.albedo32.upload(alb)) || (rc = ns.albedo64.upload(alb64)))
       return rc;
   }
   fill_obj_meta(objects, num_objects, ns.meta);
@@ -246,6 +255,7 @@ extern "C" int rt_scene_set_objects(rt_scene* s, const rt_object_desc* objects, 
   std::swap(s->f32.objs, ns.fo);
   std::swap(s->f32.objx, ns.fx);
   std::swap(s->albedo32, ns.albedo32);
+  std::swap(s->albedo64, ns.albedo64);
   if (s->objbins) std::swap(s->objbox_dev, ns.objbox);
   s->h_fo.swap(ns.h_fo);
   s->h_obj_ty.swap(ns.h_obj_ty);

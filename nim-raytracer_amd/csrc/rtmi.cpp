@@ -470,8 +470,11 @@ extern "C" int rt_scene_create(const rt_scene_desc* d, rt_scene** out_scene) {
     int rc;
     std::vector<float> alb;
     fill_albedo32(d->objects, d->num_objects, alb);
+    std::vector<double> alb64;
+    fill_albedo64(d->objects, d->num_objects, alb64);
     if ((rc = s->f32.objs.upload(fo)) || (rc = s->f32.objx.upload(fx)) || (rc = s->f32.meshes.upload(fm)) ||
-        (rc = s->f32.normals.upload(n)) || (rc = s->albedo32.upload(alb)))
+        (rc = s->f32.normals.upload(n)) || (rc = s->albedo32.upload(alb)) ||
+        (rc = s->albedo64.upload(alb64)))
       return rc;
   }
   {

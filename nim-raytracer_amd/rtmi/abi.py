@@ -161,6 +161,17 @@ class rt_aov_buffers(C.Structure):
     ]
 
 
+class rt_aov_buffers64(C.Structure):
+    _fields_ = [
+        ("alpha", C.POINTER(C.c_double)),
+        ("depth", C.POINTER(C.c_double)),
+        ("object", C.POINTER(C.c_int32)),
+        ("face", C.POINTER(C.c_int32)),
+        ("normal", C.POINTER(C.c_double)),
+        ("albedo", C.POINTER(C.c_double)),
+    ]
+
+
 RT_QUEUE_STOPPED, RT_QUEUE_RUNNING, RT_QUEUE_SHUTDOWN = 0, 1, 2
 
 
@@ -288,6 +299,10 @@ SIGNATURES = {
                                         _P, C.POINTER(rt_stats)]),
     "rt_render_aovs": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(rt_aov_buffers), C.c_int32, C.c_int32,
                                  C.POINTER(rt_stats)]),
+    "rt_render_aovs_f64_device": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(rt_aov_buffers64), C.c_int32,
+                                            C.c_int32, _P, C.POINTER(rt_stats)]),
+    "rt_render_aovs_f64": (C.c_int, [_P, C.POINTER(rt_options), C.POINTER(rt_aov_buffers64), C.c_int32, C.c_int32,
+                                     C.POINTER(rt_stats)]),
 }
 
 

@@ -388,6 +388,19 @@ class DeviceScene:
         (a dict by channel name of contiguous arrays of those shapes and
         types; numpy arrays select the host form). With stats=True returns
         (dict, Stats)."""
+        return self._render_aovs(opts, channels, y0, y1, stream, stats, host, out, False)
+
+    def render_aovs_f64(self, opts: Options, channels=AOV_CHANNELS, y0=0, y1=None, stream=None, stats=False,
+                        host=False, out=None):
+        """The per-pixel feature buffers of the fp64 frame `opts` describes
+        (include/rtmi.h rt_aov_buffers64, rt_render_aovs_f64*): render_aovs'
+        arguments and results, with alpha, depth, normal and albedo float64.
+        normal and albedo are summed in sample order, so every channel has
+        one correct bit pattern; of opts.flags RT_FLAG_NO_BINNING and
+        RT_FLAG_F64_PER_LANE are honoured and change no byte."""
+        return self._render_aovs(opts, channels, y0, y1, stream, stats, host, out, True)
+
+    def _render_aovs(self, opts, channels, y0, y1, stream, stats, host, out, f64):
         w, h = int(opts.width), int(opts.height)
         unknown = [c for c in channels if c not in self.AOV_CHANNELS]
         if unknown:
@@ -395,17 +408,18 @@ class DeviceScene:
         out = dict(out or {})
         if any(_is_host(a) for a in out.values()):
             host = True
-        bufs = abi.rt_aov_buffers()
+        bufs = (abi.rt_aov_buffers64 if f64 else abi.rt_aov_buffers)()
+        ftype, fnp = (C.c_double, np.float64) if f64 else (C.c_float, np.float32)
         res = {}
         for c in self.AOV_CHANNELS:
             if c not in channels:
                 continue
             shape = (h, w, 3) if c in ("normal", "albedo") else (h, w)
             ints = c in ("object", "face")
-            ctype = C.c_int32 if ints else C.c_float
+            ctype = C.c_int32 if ints else ftype
             a = out.get(c)
             if host:
-                dt = np.int32 if ints else np.float32
+                dt = np.int32 if ints else fnp
                 if a is None:
                     a = np.zeros(shape, dtype=dt)
                 elif not (_is_host(a) and a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == int(np.prod(shape))):
@@ -413,7 +427,7 @@ class DeviceScene:
                 ptr = a.ctypes.data_as(C.POINTER(ctype))
             else:
                 import torch
-                dt = torch.int32 if ints else torch.float32
+                dt = torch.int32 if ints else (torch.float64 if f64 else torch.float32)
                 if a is None:
                     a = torch.zeros(shape, dtype=dt, device=f"cuda:{self.device}")
                 elif _is_host(a) or not (a.is_cuda and a.dtype == dt and a.is_contiguous()
@@ -427,9 +441,11 @@ class DeviceScene:
         pst = C.byref(st) if stats else None
         y1 = h if y1 is None else int(y1)
         if host:
-            check(lib().rt_render_aovs(self.h, C.byref(o), C.byref(bufs), int(y0), y1, pst))
+            call = lib().rt_render_aovs_f64 if f64 else lib().rt_render_aovs
+            check(call(self.h, C.byref(o), C.byref(bufs), int(y0), y1, pst))
         else:
-            check(lib().rt_render_aovs_device(self.h, C.byref(o), C.byref(bufs), int(y0), y1, _stream(stream), pst))
+            call = lib().rt_render_aovs_f64_device if f64 else lib().rt_render_aovs_device
+            check(call(self.h, C.byref(o), C.byref(bufs), int(y0), y1, _stream(stream), pst))
         return (res, Stats.from_c(st)) if stats else res
 
     def _query32_host(self, n, normals, stats, call):
