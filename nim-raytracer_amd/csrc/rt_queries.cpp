@@ -9,13 +9,14 @@
 
 #include "rt_query.h"
 #include "rt_scene.h"
+#include "rt_stage.h"
 
 namespace {
 
 constexpr uint32_t kQueryFlags = RT_QUERY_ANY_HIT | RT_QUERY_SORT;
 
-// What every query entry point checks before it takes the scene's lock.
-int query_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, const double* normals) {
+// What every hit query of either precision checks before it takes the scene's lock.
+int query_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, const void* normals) {
   if (!s) return fail(RT_E_INVALID, "null scene");
   if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
   if (flags & ~kQueryFlags) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags & ~kQueryFlags);
@@ -26,14 +27,31 @@ int query_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, 
   return RT_OK;
 }
 
-int pick_check(const rt_options* o) {
+// ... and a pick of `precision` (RT_FP64: rt_pick_pixels*, RT_FP32: rt_pick_pixels_f32*) besides
+int pick_check(const rt_options* o, int32_t precision) {
   if (!o) return fail(RT_E_INVALID, "null options");
   if (o->width <= 0 || o->height <= 0 || o->width > 65536 || o->height > 65536)
     return fail(RT_E_INVALID, "bad image size %dx%d", o->width, o->height);
-  if (o->precision != RT_FP64)
-    return fail(o->precision == RT_FP32 ? RT_E_UNSUPPORTED : RT_E_INVALID, "ray queries are float64 only (precision %d)",
+  if (o->precision == precision) return RT_OK;
+  if (precision == RT_FP32)
+    return fail(RT_E_INVALID, "rt_pick_pixels_f32 is float32 only (precision %d): rt_pick_pixels is the float64 pick",
                 o->precision);
-  return RT_OK;
+  return fail(o->precision == RT_FP32 ? RT_E_UNSUPPORTED : RT_E_INVALID, "ray queries are float64 only (precision %d)",
+              o->precision);
+}
+
+// The frame of every query entry point, after its argument checks: a batch of
+// no rays reports zero Stats; any other runs `body` with the scene's lock held
+// and its device current.
+template <class Body>
+int query_call(rt_scene* s, int64_t n, rt_stats* out, Body body) {
+  if (n == 0) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  return body();
 }
 
 // RenderParams<double> as the float64 render fills it, without a
@@ -123,10 +141,30 @@ int query_end(rt_scene* s, int blocks, hipStream_t st, unsigned long long* h) {
   return RT_OK;
 }
 
-// The device body of every hit query (the scene's lock held, its device
-// current): q's ray, hit and normal pointers are device memory.
-int query_device(rt_scene* s, const RenderParams<double>& p, QueryParams q, uint32_t flags, hipStream_t st,
-                 rt_stats* out) {
+// query_end's sums as the call's Stats. counted: the float64 kernels count
+// their intersection tests; the float32 kernels leave the slot at 0 and the
+// count is derived, as for a render: one test per object per trace call
+// (renderer.nim:54-56). primary: the rays were camera rays (a pick's, a
+// radiance query's), not a trace's — the kernels count the rays they traced
+// in that slot either way.
+rt_stats query_stats(const rt_scene* s, const unsigned long long* h, bool counted, bool primary) {
+  const unsigned long long rays = h[STAT_PRIMARY] + h[STAT_SHADOW] + h[STAT_REFL];
+  rt_stats r{};
+  r.num_primary_rays = primary ? h[STAT_PRIMARY] : 0;
+  r.num_intersection_tests = counted ? h[STAT_TESTS] : (unsigned long long)s->nobj * rays;
+  r.num_intersection_hits = h[STAT_HITS];
+  r.num_shadow_rays = h[STAT_SHADOW];
+  r.num_reflection_rays = h[STAT_REFL];
+  return r;
+}
+
+// The device body of every float64 hit query (the scene's lock held, its
+// device current): q's ray, hit and normal pointers are device memory. pick:
+// the image size of a pick (its width and height alone are read), nullptr for
+// a trace.
+int query_device(rt_scene* s, const rt_options* pick, QueryParams q, uint32_t flags, hipStream_t st, rt_stats* out) {
+  RenderParams<double> p;
+  fill_query(s, pick ? pick->width : 1, pick ? pick->height : 1, p);
   if (int rc = query_begin(s, st)) return rc;
   if (s->q_blocks_per_cu < 0) s->q_blocks_per_cu = rtmi_query_blocks_per_cu();
   if (s->q_blocks_per_cu <= 0) return fail(RT_E_DEVICE, "the ray query kernel is not resident on this device");
@@ -138,163 +176,42 @@ int query_device(rt_scene* s, const RenderParams<double>& p, QueryParams q, uint
     return fail(RT_E_DEVICE, "ray query launch failed: %s", hipGetErrorString((hipError_t)e));
   unsigned long long h[kStatSlots];
   if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
-  if (out) {
-    *out = rt_stats{};
-    out->num_primary_rays = q.xy ? h[STAT_PRIMARY] : 0;  // camera rays are a pick's; the kernel counts the rays it traced
-    out->num_intersection_tests = h[STAT_TESTS];
-    out->num_intersection_hits = h[STAT_HITS];
-  }
+  // camera rays are a pick's; the kernel counts the rays it traced
+  if (out) *out = query_stats(s, h, true, q.xy != nullptr);
   return RT_OK;
 }
 
-// Host form: the batch copied into the scene's staging buffer, queried on
-// the scene's own stream, the answers copied back. in[k]: host arrays of
-// in_bytes[k] bytes (nullptr: absent).
-int query_host(rt_scene* s, const RenderParams<double>& p, int64_t n, const void* const in[4], const size_t in_bytes[4],
-               uint32_t flags, rt_hit* hits, double* normals, rt_stats* out) {
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off[6], total = 0;
-  for (int k = 0; k < 4; ++k) {
-    off[k] = total;
-    total += in[k] ? al(in_bytes[k]) : 0;
-  }
-  off[4] = total;
-  total += al((size_t)n * sizeof(rt_hit));
-  off[5] = total;
-  total += normals ? al((size_t)n * 3 * sizeof(double)) : 0;
-  hipStream_t st = s->stream;
-  if (s->q_stage.n < total) {
-    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
-    if (int rc = s->q_stage.alloc(total)) return rc;
-  }
-  unsigned char* base = s->q_stage.p;
-  // the staging buffer's last user was a query on this stream, or has been waited for
-  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
-  for (int k = 0; k < 4; ++k)
-    if (in[k]) HIP_TRY(hipMemcpyAsync(base + off[k], in[k], in_bytes[k], hipMemcpyHostToDevice, st));
-  QueryParams q{};
-  q.orig = in[0] ? (const double*)(base + off[0]) : nullptr;
-  q.dir = in[1] ? (const double*)(base + off[1]) : nullptr;
-  q.tnear = in[2] ? (const double*)(base + off[2]) : nullptr;
-  q.xy = in[3] ? (const double*)(base + off[3]) : nullptr;
-  q.hits = (QueryHit*)(base + off[4]);
-  q.normals = normals ? (double*)(base + off[5]) : nullptr;
-  q.n = n;
-  if (int rc = query_device(s, p, q, flags, st, out)) return rc;
-  HIP_TRY(hipMemcpyAsync(hits, base + off[4], (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
-  if (normals)
-    HIP_TRY(hipMemcpyAsync(normals, base + off[5], (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return RT_OK;
-}
-
-}  // namespace
-
-static_assert(sizeof(rt_hit) == sizeof(QueryHit), "rt_hit layout");
-
-extern "C" int rt_trace_rays_device(rt_scene* s, int64_t n, const double* d_orig, const double* d_dir,
-                                    const double* d_tnear, uint32_t flags, rt_hit* d_hits, double* d_normals,
-                                    void* stream, rt_stats* out) {
-  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
-  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  RenderParams<double> p;
-  fill_query(s, 1, 1, p);
-  QueryParams q{};
-  q.orig = d_orig;
-  q.dir = d_dir;
-  q.tnear = d_tnear;
-  q.hits = (QueryHit*)d_hits;
-  q.normals = d_normals;
-  q.n = n;
-  return query_device(s, p, q, flags, (hipStream_t)stream, out);
-}
-
-extern "C" int rt_trace_rays(rt_scene* s, int64_t n, const double* orig, const double* dir, const double* tnear,
-                             uint32_t flags, rt_hit* hits, double* normals, rt_stats* out) {
-  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
-  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  RenderParams<double> p;
-  fill_query(s, 1, 1, p);
-  const size_t v3 = (size_t)n * 3 * sizeof(double);
-  const void* const in[4] = {orig, dir, tnear, nullptr};
-  const size_t bytes[4] = {v3, v3, (size_t)n * sizeof(double), 0};
-  return query_host(s, p, n, in, bytes, flags, hits, normals, out);
-}
-
-extern "C" int rt_pick_pixels_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_xy, uint32_t flags,
-                                     rt_hit* d_hits, double* d_normals, void* stream, rt_stats* out) {
-  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
-  if (int rc = pick_check(o)) return rc;
-  if (n > 0 && !d_xy) return fail(RT_E_INVALID, "null pixel positions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  RenderParams<double> p;
-  fill_query(s, o->width, o->height, p);
-  QueryParams q{};
-  q.xy = d_xy;
-  q.hits = (QueryHit*)d_hits;
-  q.normals = d_normals;
-  q.n = n;
-  return query_device(s, p, q, flags, (hipStream_t)stream, out);
-}
-
-extern "C" int rt_pick_pixels(rt_scene* s, const rt_options* o, int64_t n, const double* xy, uint32_t flags,
-                              rt_hit* hits, double* normals, rt_stats* out) {
-  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
-  if (int rc = pick_check(o)) return rc;
-  if (n > 0 && !xy) return fail(RT_E_INVALID, "null pixel positions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  RenderParams<double> p;
-  fill_query(s, o->width, o->height, p);
-  const void* const in[4] = {nullptr, nullptr, nullptr, xy};
-  const size_t bytes[4] = {0, 0, 0, (size_t)n * 2 * sizeof(double)};
-  return query_host(s, p, n, in, bytes, flags, hits, normals, out);
-}
-
-// ---- radiance queries (rt_shade_rays*) --------------------------------------
-namespace {
-
-// What both shade entry points check before they take the scene's lock.
-int shade_check(const rt_scene* s, const rt_options* o, int64_t n, int32_t group, uint32_t flags, const void* rgb,
-                const void* rgb32) {
+// ---- radiance queries: checks and device bodies -----------------------------
+// What the four radiance-query entry points check before they take the scene's
+// lock. f32: rt_shade_rays_f32* (one output, rgb32), else rt_shade_rays* (rgb
+// and / or rgb32). The float32 call names missing rays before a missing
+// output and the wrong precision, the float64 call after them.
+int shade_check(const rt_scene* s, const rt_options* o, int64_t n, int32_t group, uint32_t flags, bool f32,
+                const void* orig, const void* dir, const void* rgb, const void* rgb32) {
   if (!s) return fail(RT_E_INVALID, "null scene");
   if (!o) return fail(RT_E_INVALID, "null options");
   if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
   if (flags & ~(uint32_t)RT_QUERY_SORT)
-    return fail(RT_E_INVALID, "rt_shade_rays takes RT_QUERY_SORT only (flags 0x%x)", flags);
+    return fail(RT_E_INVALID, "%s takes RT_QUERY_SORT only (flags 0x%x)", f32 ? "rt_shade_rays_f32" : "rt_shade_rays",
+                flags);
   if (group < 1) return fail(RT_E_INVALID, "group %d (at least 1)", group);
   if (n % group) return fail(RT_E_INVALID, "%lld rays are not a whole number of groups of %d", (long long)n, group);
-  if (n > 0 && !rgb && !rgb32) return fail(RT_E_INVALID, "null rgb and rgb32");
-  if (o->precision != RT_FP64)
+  const bool no_rays = n > 0 && (!orig || !dir);
+  if (f32 && no_rays) return fail(RT_E_INVALID, "null ray origins or directions");
+  if (n > 0 && !rgb && !rgb32) return fail(RT_E_INVALID, "%s", f32 ? "null rgb" : "null rgb and rgb32");
+  if (f32 && o->precision != RT_FP32)
+    return fail(RT_E_INVALID, "rt_shade_rays_f32 is float32 only (precision %d): rt_shade_rays is the float64 query",
+                o->precision);
+  if (!f32 && o->precision != RT_FP64)
     return fail(o->precision == RT_FP32 ? RT_E_UNSUPPORTED : RT_E_INVALID,
                 "radiance queries are float64 only (precision %d)", o->precision);
   if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
+  if (no_rays) return fail(RT_E_INVALID, "null ray origins or directions");
   return RT_OK;
 }
 
-// The device body of both forms (the scene's lock held, its device current):
-// q.orig / q.dir and the outputs are device memory.
+// The device body of both forms of rt_shade_rays (the scene's lock held, its
+// device current): q.orig / q.dir and the outputs are device memory.
 int shade_device(rt_scene* s, const rt_options* o, QueryParams q, int32_t group, uint32_t flags, double* d_rgb,
                  float* d_rgb32, hipStream_t st, rt_stats* out) {
   // as check_options says it for a render (any_reflective: under the lock, rt_scene_set_objects may flip it)
@@ -332,100 +249,12 @@ int shade_device(rt_scene* s, const rt_options* o, QueryParams q, int32_t group,
   }
   unsigned long long h[kStatSlots];
   if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
-  if (out) {
-    out->num_primary_rays = h[STAT_PRIMARY];
-    out->num_intersection_tests = h[STAT_TESTS];
-    out->num_intersection_hits = h[STAT_HITS];
-    out->num_shadow_rays = h[STAT_SHADOW];
-    out->num_reflection_rays = h[STAT_REFL];
-  }
+  if (out) *out = query_stats(s, h, true, true);
   return RT_OK;
 }
 
-}  // namespace
-
-extern "C" int rt_shade_rays_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_orig,
-                                    const double* d_dir, int32_t group, uint32_t flags, double* d_rgb, float* d_rgb32,
-                                    void* stream, rt_stats* out) {
-  if (int rc = shade_check(s, o, n, group, flags, d_rgb, d_rgb32)) return rc;
-  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  QueryParams q{};
-  q.orig = d_orig;
-  q.dir = d_dir;
-  q.n = n;
-  return shade_device(s, o, q, group, flags, d_rgb, d_rgb32, (hipStream_t)stream, out);
-}
-
-extern "C" int rt_shade_rays(rt_scene* s, const rt_options* o, int64_t n, const double* orig, const double* dir,
-                             int32_t group, uint32_t flags, double* rgb, float* rgb32, rt_stats* out) {
-  if (int rc = shade_check(s, o, n, group, flags, rgb, rgb32)) return rc;
-  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  // the batch copied into the scene's staging buffer, shaded on the scene's
-  // own stream, the colours copied back (query_host's discipline)
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t v3 = (size_t)n * 3 * sizeof(double), ng = (size_t)(n / group);
-  const size_t off_dir = al(v3), off_rgb = off_dir + al(v3);
-  const size_t off_rgb32 = off_rgb + (rgb ? al(ng * 3 * sizeof(double)) : 0);
-  const size_t total = off_rgb32 + (rgb32 ? al(ng * 3 * sizeof(float)) : 0);
-  hipStream_t st = s->stream;
-  if (s->q_stage.n < total) {
-    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
-    if (int rc = s->q_stage.alloc(total)) return rc;
-  }
-  unsigned char* base = s->q_stage.p;
-  // the staging buffer's last user was a query on this stream, or has been waited for
-  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
-  HIP_TRY(hipMemcpyAsync(base, orig, v3, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(base + off_dir, dir, v3, hipMemcpyHostToDevice, st));
-  QueryParams q{};
-  q.orig = (const double*)base;
-  q.dir = (const double*)(base + off_dir);
-  q.n = n;
-  double* d_rgb = rgb ? (double*)(base + off_rgb) : nullptr;
-  float* d_rgb32 = rgb32 ? (float*)(base + off_rgb32) : nullptr;
-  if (int rc = shade_device(s, o, q, group, flags, d_rgb, d_rgb32, st, out)) return rc;
-  if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (rgb32) HIP_TRY(hipMemcpyAsync(rgb32, d_rgb32, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return RT_OK;
-}
-
-// ---- float32 radiance queries (rt_shade_rays_f32*) --------------------------
-namespace {
-
-// What both float32 shade entry points check before they take the scene's lock.
-int shade32_check(const rt_scene* s, const rt_options* o, int64_t n, int32_t group, uint32_t flags, const void* orig,
-                  const void* dir, const void* rgb) {
-  if (!s) return fail(RT_E_INVALID, "null scene");
-  if (!o) return fail(RT_E_INVALID, "null options");
-  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
-  if (flags & ~(uint32_t)RT_QUERY_SORT)
-    return fail(RT_E_INVALID, "rt_shade_rays_f32 takes RT_QUERY_SORT only (flags 0x%x)", flags);
-  if (group < 1) return fail(RT_E_INVALID, "group %d (at least 1)", group);
-  if (n % group) return fail(RT_E_INVALID, "%lld rays are not a whole number of groups of %d", (long long)n, group);
-  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n > 0 && !rgb) return fail(RT_E_INVALID, "null rgb");
-  if (o->precision != RT_FP32)
-    return fail(RT_E_INVALID, "rt_shade_rays_f32 is float32 only (precision %d): rt_shade_rays is the float64 query",
-                o->precision);
-  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
-  return RT_OK;
-}
-
-// The device body of both forms (the scene's lock held, its device current):
-// q.orig / q.dir and d_rgb are device memory.
+// The device body of both forms of rt_shade_rays_f32 (the scene's lock held,
+// its device current): q.orig / q.dir and d_rgb are device memory.
 int shade32_device(rt_scene* s, const rt_options* o, Shade32Params q, int32_t group, uint32_t flags, float* d_rgb,
                    hipStream_t st, rt_stats* out) {
   // as check_options says it for a render (any_reflective: under the lock, rt_scene_set_objects may flip it)
@@ -472,101 +301,11 @@ int shade32_device(rt_scene* s, const rt_options* o, Shade32Params q, int32_t gr
   }
   unsigned long long h[kStatSlots];
   if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
-  if (out) {
-    // one test per object per trace call (renderer.nim:54-56); the float32
-    // kernels leave the slot at 0 and the count is derived, as for a render
-    const unsigned long long rays = h[STAT_PRIMARY] + h[STAT_SHADOW] + h[STAT_REFL];
-    out->num_primary_rays = h[STAT_PRIMARY];
-    out->num_intersection_tests = (unsigned long long)s->nobj * rays;
-    out->num_intersection_hits = h[STAT_HITS];
-    out->num_shadow_rays = h[STAT_SHADOW];
-    out->num_reflection_rays = h[STAT_REFL];
-  }
+  if (out) *out = query_stats(s, h, false, true);
   return RT_OK;
 }
 
-}  // namespace
-
-extern "C" int rt_shade_rays_f32_device(rt_scene* s, const rt_options* o, int64_t n, const float* d_orig,
-                                        const float* d_dir, int32_t group, uint32_t flags, float* d_rgb, void* stream,
-                                        rt_stats* out) {
-  if (int rc = shade32_check(s, o, n, group, flags, d_orig, d_dir, d_rgb)) return rc;
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  Shade32Params q{};
-  q.orig = d_orig;
-  q.dir = d_dir;
-  q.n = n;
-  return shade32_device(s, o, q, group, flags, d_rgb, (hipStream_t)stream, out);
-}
-
-extern "C" int rt_shade_rays_f32(rt_scene* s, const rt_options* o, int64_t n, const float* orig, const float* dir,
-                                 int32_t group, uint32_t flags, float* rgb, rt_stats* out) {
-  if (int rc = shade32_check(s, o, n, group, flags, orig, dir, rgb)) return rc;
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  // the batch copied into the scene's staging buffer, shaded on the scene's
-  // own stream, the colours copied back (query_host's discipline)
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t v3 = (size_t)n * 3 * sizeof(float), ng = (size_t)(n / group);
-  const size_t off_dir = al(v3), off_rgb = off_dir + al(v3);
-  const size_t total = off_rgb + al(ng * 3 * sizeof(float));
-  hipStream_t st = s->stream;
-  if (s->q_stage.n < total) {
-    if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
-    if (int rc = s->q_stage.alloc(total)) return rc;
-  }
-  unsigned char* base = s->q_stage.p;
-  // the staging buffer's last user was a query on this stream, or has been waited for
-  if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
-  HIP_TRY(hipMemcpyAsync(base, orig, v3, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(base + off_dir, dir, v3, hipMemcpyHostToDevice, st));
-  Shade32Params q{};
-  q.orig = (const float*)base;
-  q.dir = (const float*)(base + off_dir);
-  q.n = n;
-  float* d_rgb = (float*)(base + off_rgb);
-  if (int rc = shade32_device(s, o, q, group, flags, d_rgb, st, out)) return rc;
-  HIP_TRY(hipMemcpyAsync(rgb, d_rgb, ng * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return RT_OK;
-}
-
-// ---- float32 ray queries and picks (rt_trace_rays_f32* / rt_pick_pixels_f32*) ----
-static_assert(sizeof(rt_hit32) == sizeof(Hit32), "rt_hit32 layout");
-
-namespace {
-
-// What every float32 hit query checks before it takes the scene's lock.
-int trace32_check(const rt_scene* s, int64_t n, uint32_t flags, const void* hits, const void* normals) {
-  if (!s) return fail(RT_E_INVALID, "null scene");
-  if (n < 0) return fail(RT_E_INVALID, "negative ray count %lld", (long long)n);
-  if (flags & ~kQueryFlags) return fail(RT_E_INVALID, "unknown query flags 0x%x", flags & ~kQueryFlags);
-  if ((flags & RT_QUERY_ANY_HIT) && normals)
-    return fail(RT_E_INVALID, "normals are not available with RT_QUERY_ANY_HIT");
-  if (n > 0 && !hits) return fail(RT_E_INVALID, "null hits");
-  if (n > INT32_MAX) return fail(RT_E_UNSUPPORTED, "%lld rays in one batch (at most 2^31 - 1)", (long long)n);
-  return RT_OK;
-}
-
-int pick32_check(const rt_options* o) {
-  if (!o) return fail(RT_E_INVALID, "null options");
-  if (o->width <= 0 || o->height <= 0 || o->width > 65536 || o->height > 65536)
-    return fail(RT_E_INVALID, "bad image size %dx%d", o->width, o->height);
-  if (o->precision != RT_FP32)
-    return fail(RT_E_INVALID, "rt_pick_pixels_f32 is float32 only (precision %d): rt_pick_pixels is the float64 pick",
-                o->precision);
-  return RT_OK;
-}
-
+// ---- float32 ray queries and picks: the device body --------------------------
 // The device body of every float32 hit query (the scene's lock held, its
 // device current): q's ray, hit and normal pointers are device memory. pick:
 // the image size of a pick (its width and height alone are read), nullptr for
@@ -609,129 +348,262 @@ int trace32_device(rt_scene* s, const rt_options* pick, Trace32Params q, uint32_
     return fail(RT_E_DEVICE, "float32 ray query launch failed: %s", hipGetErrorString((hipError_t)e));
   unsigned long long h[kStatSlots];
   if (int rc = query_end(s, blocks, st, out ? h : nullptr)) return rc;
-  if (out) {
-    // one test per object per trace call (renderer.nim:54-56): derived, as
-    // shade32_device derives it; camera rays are a pick's
-    *out = rt_stats{};
-    out->num_primary_rays = pick ? h[STAT_PRIMARY] : 0;
-    out->num_intersection_tests = (unsigned long long)s->nobj * h[STAT_PRIMARY];
-    out->num_intersection_hits = h[STAT_HITS];
-  }
+  if (out) *out = query_stats(s, h, false, pick != nullptr);  // camera rays are a pick's
   return RT_OK;
 }
 
-// Host form: the batch copied into the scene's staging buffer, queried on the
-// scene's own stream, the answers copied back (query_host's discipline).
-// in[k]: host arrays of in_bytes[k] bytes (nullptr: absent): orig, dir, tnear, xy.
-int trace32_host(rt_scene* s, const rt_options* pick, int64_t n, const void* const in[4], const size_t in_bytes[4],
-                 uint32_t flags, rt_hit32* hits, float* normals, rt_stats* out) {
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off[6], total = 0;
-  for (int k = 0; k < 4; ++k) {
-    off[k] = total;
-    total += in[k] ? al(in_bytes[k]) : 0;
-  }
-  off[4] = total;
-  total += al((size_t)n * sizeof(rt_hit32));
-  off[5] = total;
-  total += normals ? al((size_t)n * 3 * sizeof(float)) : 0;
-  hipStream_t st = s->stream;
+// ---- the host forms' staging (rt_stage.h) ------------------------------------
+// A batch is copied into the scene's staging buffer, queried on the scene's
+// own stream, and its answers copied back.
+
+// The staging buffer with room for `total` bytes, `st` ordered after its last
+// user: a query on this stream, or one that is waited for.
+int stage_reserve(rt_scene* s, size_t total, hipStream_t st, unsigned char** base) {
   if (s->q_stage.n < total) {
     if (s->q_done_rec) HIP_TRY(hipEventSynchronize(s->q_done));
     if (int rc = s->q_stage.alloc(total)) return rc;
   }
-  unsigned char* base = s->q_stage.p;
-  // the staging buffer's last user was a query on this stream, or has been waited for
+  *base = s->q_stage.p;
   if (s->q_done_rec && st != s->q_stream) HIP_TRY(hipStreamWaitEvent(st, s->q_done, 0));
-  for (int k = 0; k < 4; ++k)
-    if (in[k]) HIP_TRY(hipMemcpyAsync(base + off[k], in[k], in_bytes[k], hipMemcpyHostToDevice, st));
-  Trace32Params q{};
-  q.orig = in[0] ? (const float*)(base + off[0]) : nullptr;
-  q.dir = in[1] ? (const float*)(base + off[1]) : nullptr;
-  q.tnear = in[2] ? (const float*)(base + off[2]) : nullptr;
-  q.xy = in[3] ? (const float*)(base + off[3]) : nullptr;
-  q.hits = (Hit32*)(base + off[4]);
-  q.normals = normals ? (float*)(base + off[5]) : nullptr;
+  return RT_OK;
+}
+
+// A host array of `count` T into its slot at `dst` (nullptr: absent, and
+// *dev says so)
+template <class T>
+int stage_in(void* dst, const T* host, size_t count, hipStream_t st, const T** dev) {
+  *dev = host ? (const T*)dst : nullptr;
+  if (host) HIP_TRY(hipMemcpyAsync(dst, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+  return RT_OK;
+}
+
+// ... and `count` T of a slot back into the host array that wants them
+template <class T>
+int stage_out(T* host, const void* src, size_t count, hipStream_t st) {
+  if (host) HIP_TRY(hipMemcpyAsync(host, src, count * sizeof(T), hipMemcpyDeviceToHost, st));
+  return RT_OK;
+}
+
+// What a hit query's host form is made of in each precision
+struct Hits64 {
+  using Scalar = double;
+  using Hit = rt_hit;
+  using DevHit = QueryHit;
+  using Params = QueryParams;
+  static constexpr auto device = &query_device;
+};
+struct Hits32 {
+  using Scalar = float;
+  using Hit = rt_hit32;
+  using DevHit = Hit32;
+  using Params = Trace32Params;
+  static constexpr auto device = &trace32_device;
+};
+
+// Host form of every hit query: orig / dir / tnear (a trace, pick = nullptr) or
+// xy (a pick) are host arrays, nullptr where absent.
+template <class K>
+int query_host(rt_scene* s, const rt_options* pick, int64_t n, const typename K::Scalar* orig,
+               const typename K::Scalar* dir, const typename K::Scalar* tnear, const typename K::Scalar* xy,
+               uint32_t flags, typename K::Hit* hits, typename K::Scalar* normals, rt_stats* out) {
+  using S = typename K::Scalar;
+  static_assert(sizeof(typename K::Hit) == 16 && sizeof(typename K::DevHit) == 16, "hit_stage_layout's hits");
+  const size_t N = (size_t)n;
+  const StageLayout l = hit_stage_layout(N, sizeof(S), orig, dir, tnear, xy, normals);
+  hipStream_t st = s->stream;
+  unsigned char* base = nullptr;
+  if (int rc = stage_reserve(s, l.total, st, &base)) return rc;
+  typename K::Params q{};
+  if (int rc = stage_in(base + l.off[0], orig, N * 3, st, &q.orig)) return rc;
+  if (int rc = stage_in(base + l.off[1], dir, N * 3, st, &q.dir)) return rc;
+  if (int rc = stage_in(base + l.off[2], tnear, N, st, &q.tnear)) return rc;
+  if (int rc = stage_in(base + l.off[3], xy, N * 2, st, &q.xy)) return rc;
+  q.hits = (typename K::DevHit*)(base + l.off[4]);
+  q.normals = normals ? (S*)(base + l.off[5]) : nullptr;
   q.n = n;
-  if (int rc = trace32_device(s, pick, q, flags, st, out)) return rc;
-  HIP_TRY(hipMemcpyAsync(hits, base + off[4], (size_t)n * sizeof(rt_hit32), hipMemcpyDeviceToHost, st));
-  if (normals)
-    HIP_TRY(hipMemcpyAsync(normals, base + off[5], (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (int rc = K::device(s, pick, q, flags, st, out)) return rc;
+  if (int rc = stage_out(hits, q.hits, N, st)) return rc;
+  if (int rc = stage_out(normals, q.normals, N * 3, st)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   return RT_OK;
 }
 
 }  // namespace
 
+static_assert(sizeof(rt_hit) == sizeof(QueryHit), "rt_hit layout");
+static_assert(sizeof(rt_hit32) == sizeof(Hit32), "rt_hit32 layout");
+
+// ---- ray queries and picks (rt_trace_rays* / rt_pick_pixels*, and their _f32 forms) ----
+extern "C" int rt_trace_rays_device(rt_scene* s, int64_t n, const double* d_orig, const double* d_dir,
+                                    const double* d_tnear, uint32_t flags, rt_hit* d_hits, double* d_normals,
+                                    void* stream, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  return query_call(s, n, out, [&] {
+    QueryParams q{};
+    q.orig = d_orig;
+    q.dir = d_dir;
+    q.tnear = d_tnear;
+    q.hits = (QueryHit*)d_hits;
+    q.normals = d_normals;
+    q.n = n;
+    return query_device(s, nullptr, q, flags, (hipStream_t)stream, out);
+  });
+}
+
+extern "C" int rt_trace_rays(rt_scene* s, int64_t n, const double* orig, const double* dir, const double* tnear,
+                             uint32_t flags, rt_hit* hits, double* normals, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
+  if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
+  return query_call(s, n, out, [&] {
+    return query_host<Hits64>(s, nullptr, n, orig, dir, tnear, nullptr, flags, hits, normals, out);
+  });
+}
+
+extern "C" int rt_pick_pixels_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_xy, uint32_t flags,
+                                     rt_hit* d_hits, double* d_normals, void* stream, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (int rc = pick_check(o, RT_FP64)) return rc;
+  if (n > 0 && !d_xy) return fail(RT_E_INVALID, "null pixel positions");
+  return query_call(s, n, out, [&] {
+    QueryParams q{};
+    q.xy = d_xy;
+    q.hits = (QueryHit*)d_hits;
+    q.normals = d_normals;
+    q.n = n;
+    return query_device(s, o, q, flags, (hipStream_t)stream, out);
+  });
+}
+
+extern "C" int rt_pick_pixels(rt_scene* s, const rt_options* o, int64_t n, const double* xy, uint32_t flags,
+                              rt_hit* hits, double* normals, rt_stats* out) {
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
+  if (int rc = pick_check(o, RT_FP64)) return rc;
+  if (n > 0 && !xy) return fail(RT_E_INVALID, "null pixel positions");
+  return query_call(s, n, out, [&] {
+    return query_host<Hits64>(s, o, n, nullptr, nullptr, nullptr, xy, flags, hits, normals, out);
+  });
+}
+
 extern "C" int rt_trace_rays_f32_device(rt_scene* s, int64_t n, const float* d_orig, const float* d_dir,
                                         const float* d_tnear, uint32_t flags, rt_hit32* d_hits, float* d_normals,
                                         void* stream, rt_stats* out) {
-  if (int rc = trace32_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
   if (n > 0 && (!d_orig || !d_dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  Trace32Params q{};
-  q.orig = d_orig;
-  q.dir = d_dir;
-  q.tnear = d_tnear;
-  q.hits = (Hit32*)d_hits;
-  q.normals = d_normals;
-  q.n = n;
-  return trace32_device(s, nullptr, q, flags, (hipStream_t)stream, out);
+  return query_call(s, n, out, [&] {
+    Trace32Params q{};
+    q.orig = d_orig;
+    q.dir = d_dir;
+    q.tnear = d_tnear;
+    q.hits = (Hit32*)d_hits;
+    q.normals = d_normals;
+    q.n = n;
+    return trace32_device(s, nullptr, q, flags, (hipStream_t)stream, out);
+  });
 }
 
 extern "C" int rt_trace_rays_f32(rt_scene* s, int64_t n, const float* orig, const float* dir, const float* tnear,
                                  uint32_t flags, rt_hit32* hits, float* normals, rt_stats* out) {
-  if (int rc = trace32_check(s, n, flags, hits, normals)) return rc;
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
   if (n > 0 && (!orig || !dir)) return fail(RT_E_INVALID, "null ray origins or directions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  const size_t v3 = (size_t)n * 3 * sizeof(float);
-  const void* const in[4] = {orig, dir, tnear, nullptr};
-  const size_t bytes[4] = {v3, v3, (size_t)n * sizeof(float), 0};
-  return trace32_host(s, nullptr, n, in, bytes, flags, hits, normals, out);
+  return query_call(s, n, out, [&] {
+    return query_host<Hits32>(s, nullptr, n, orig, dir, tnear, nullptr, flags, hits, normals, out);
+  });
 }
 
 extern "C" int rt_pick_pixels_f32_device(rt_scene* s, const rt_options* o, int64_t n, const float* d_xy,
                                          uint32_t flags, rt_hit32* d_hits, float* d_normals, void* stream,
                                          rt_stats* out) {
-  if (int rc = trace32_check(s, n, flags, d_hits, d_normals)) return rc;
-  if (int rc = pick32_check(o)) return rc;
+  if (int rc = query_check(s, n, flags, d_hits, d_normals)) return rc;
+  if (int rc = pick_check(o, RT_FP32)) return rc;
   if (n > 0 && !d_xy) return fail(RT_E_INVALID, "null pixel positions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  Trace32Params q{};
-  q.xy = d_xy;
-  q.hits = (Hit32*)d_hits;
-  q.normals = d_normals;
-  q.n = n;
-  return trace32_device(s, o, q, flags, (hipStream_t)stream, out);
+  return query_call(s, n, out, [&] {
+    Trace32Params q{};
+    q.xy = d_xy;
+    q.hits = (Hit32*)d_hits;
+    q.normals = d_normals;
+    q.n = n;
+    return trace32_device(s, o, q, flags, (hipStream_t)stream, out);
+  });
 }
 
 extern "C" int rt_pick_pixels_f32(rt_scene* s, const rt_options* o, int64_t n, const float* xy, uint32_t flags,
                                   rt_hit32* hits, float* normals, rt_stats* out) {
-  if (int rc = trace32_check(s, n, flags, hits, normals)) return rc;
-  if (int rc = pick32_check(o)) return rc;
+  if (int rc = query_check(s, n, flags, hits, normals)) return rc;
+  if (int rc = pick_check(o, RT_FP32)) return rc;
   if (n > 0 && !xy) return fail(RT_E_INVALID, "null pixel positions");
-  if (n == 0) {
-    if (out) *out = rt_stats{};
+  return query_call(s, n, out, [&] {
+    return query_host<Hits32>(s, o, n, nullptr, nullptr, nullptr, xy, flags, hits, normals, out);
+  });
+}
+
+// ---- radiance queries (rt_shade_rays* / rt_shade_rays_f32*) ------------------
+extern "C" int rt_shade_rays_device(rt_scene* s, const rt_options* o, int64_t n, const double* d_orig,
+                                    const double* d_dir, int32_t group, uint32_t flags, double* d_rgb, float* d_rgb32,
+                                    void* stream, rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, false, d_orig, d_dir, d_rgb, d_rgb32)) return rc;
+  return query_call(s, n, out, [&] {
+    QueryParams q{};
+    q.orig = d_orig;
+    q.dir = d_dir;
+    q.n = n;
+    return shade_device(s, o, q, group, flags, d_rgb, d_rgb32, (hipStream_t)stream, out);
+  });
+}
+
+extern "C" int rt_shade_rays(rt_scene* s, const rt_options* o, int64_t n, const double* orig, const double* dir,
+                             int32_t group, uint32_t flags, double* rgb, float* rgb32, rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, false, orig, dir, rgb, rgb32)) return rc;
+  return query_call(s, n, out, [&]() -> int {
+    const size_t N = (size_t)n, ng = (size_t)(n / group);
+    const StageLayout l = shade_stage_layout(N, (size_t)group, sizeof(double), rgb, rgb32);
+    hipStream_t st = s->stream;
+    unsigned char* base = nullptr;
+    if (int rc = stage_reserve(s, l.total, st, &base)) return rc;
+    QueryParams q{};
+    if (int rc = stage_in(base + l.off[0], orig, N * 3, st, &q.orig)) return rc;
+    if (int rc = stage_in(base + l.off[1], dir, N * 3, st, &q.dir)) return rc;
+    q.n = n;
+    double* d_rgb = rgb ? (double*)(base + l.off[2]) : nullptr;
+    float* d_rgb32 = rgb32 ? (float*)(base + l.off[3]) : nullptr;
+    if (int rc = shade_device(s, o, q, group, flags, d_rgb, d_rgb32, st, out)) return rc;
+    if (int rc = stage_out(rgb, d_rgb, ng * 3, st)) return rc;
+    if (int rc = stage_out(rgb32, d_rgb32, ng * 3, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  const void* const in[4] = {nullptr, nullptr, nullptr, xy};
-  const size_t bytes[4] = {0, 0, 0, (size_t)n * 2 * sizeof(float)};
-  return trace32_host(s, o, n, in, bytes, flags, hits, normals, out);
+  });
+}
+
+extern "C" int rt_shade_rays_f32_device(rt_scene* s, const rt_options* o, int64_t n, const float* d_orig,
+                                        const float* d_dir, int32_t group, uint32_t flags, float* d_rgb, void* stream,
+                                        rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, true, d_orig, d_dir, nullptr, d_rgb)) return rc;
+  return query_call(s, n, out, [&] {
+    Shade32Params q{};
+    q.orig = d_orig;
+    q.dir = d_dir;
+    q.n = n;
+    return shade32_device(s, o, q, group, flags, d_rgb, (hipStream_t)stream, out);
+  });
+}
+
+extern "C" int rt_shade_rays_f32(rt_scene* s, const rt_options* o, int64_t n, const float* orig, const float* dir,
+                                 int32_t group, uint32_t flags, float* rgb, rt_stats* out) {
+  if (int rc = shade_check(s, o, n, group, flags, true, orig, dir, nullptr, rgb)) return rc;
+  return query_call(s, n, out, [&]() -> int {
+    const size_t N = (size_t)n, ng = (size_t)(n / group);
+    const StageLayout l = shade_stage_layout(N, (size_t)group, sizeof(float), false, true);
+    hipStream_t st = s->stream;
+    unsigned char* base = nullptr;
+    if (int rc = stage_reserve(s, l.total, st, &base)) return rc;
+    Shade32Params q{};
+    if (int rc = stage_in(base + l.off[0], orig, N * 3, st, &q.orig)) return rc;
+    if (int rc = stage_in(base + l.off[1], dir, N * 3, st, &q.dir)) return rc;
+    q.n = n;
+    float* d_rgb = (float*)(base + l.off[3]);
+    if (int rc = shade32_device(s, o, q, group, flags, d_rgb, st, out)) return rc;
+    if (int rc = stage_out(rgb, d_rgb, ng * 3, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+  });
 }

@@ -6,8 +6,8 @@
 #include <cstring>
 
 #include "rt_aov64.h"
-#include "rt_aov_stage.h"
 #include "rt_scene.h"
+#include "rt_stage.h"
 
 namespace rtmi {
 
@@ -715,6 +715,15 @@ void mapping_words(const Mapping& mp, const Plan& pl, int spp, FastParams& p) {
   }
 }
 
+// This call's pixel lists (frame_build made them) for a float32 kernel; with
+// one pixel per wave (records) its pixel records besides.
+void pixel_lists(const rt_scene* s, bool records, FastParams& p) {
+  p.pix_slots = s->fr.slots.p;
+  p.pix_cnt = s->fr.info.p;
+  p.slot_lg = s->fr.slot_lg;
+  if (records) p.pix_info = s->fr.info.p;
+}
+
 // The float32 launch's parameters and plan, and this call's camera-dependent
 // data built on the device (rt_frame.h) in stream order before the render
 // kernels: the mesh's camera-ray lists (>= 16 samples per pixel), the object
@@ -800,10 +809,7 @@ int fill_fast(rt_scene* s, const rt_options* o, const Mapping& mp, float* fb, Fa
     return rc;
   }
   if (lists) {
-    p.pix_slots = s->fr.slots.p;
-    p.pix_cnt = s->fr.info.p;
-    p.slot_lg = s->fr.slot_lg;
-    if (pl.records) p.pix_info = s->fr.info.p;
+    pixel_lists(s, pl.records, p);
     *split = pl.two_class;
   }
   if (s->objbins) {
@@ -895,16 +901,22 @@ void fill_params(rt_scene* s, const PrecisionData<R>& pd, const rt_options* o, c
   *blocks = (int)std::max(1LL, std::min<long long>(want, cap));
 }
 
-// The float64 call: its pixel records (when the scene has skip planes), then
-// k_render_px64 or k_render. *launched: blocks of the render kernel.
-int launch_f64(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, int* launched) {
-  RenderParams<double> p;
-  int blocks = 1;
-  fill_params<double>(s, s->f64, o, mp, d_out, p, &blocks);
-  s->last_general = p.ngroups;
-  if (p.ngroups == 0) return RT_OK;
+// What a float64 call of either kind — a render (launch_f64) or a feature-buffer
+// call (aov64_device) — prepares for its kernel after fill_params:
+//  - the stochastic samplers' table scratch;
+//  - this call's pixel records (the float32 path's build, one launch set) when
+//    `binning` and the scene has skip planes: a pixel whose camera rays provably
+//    miss the mesh skips their traversal, and its shadow rays to the lights its
+//    skip bits clear skip theirs — the same answers (the traversal would find no
+//    face), so frames and Stats stay bit-exact (tests/test_gpu_parity.py);
+//  - with one pixel per wave (px_wave; akGrid with >= 64 samples per pixel): the
+//    pixel lists its camera rays search, and the grid of a kernel that takes
+//    `batch` pixels per item and keeps blocks_per_cu blocks resident.
+// *lists: the pixel lists exist.
+int prepare_f64(rt_scene* s, const rt_options* o, const Mapping& mp, bool binning, bool px_wave, int batch,
+                int blocks_per_cu, RenderParams<double>& p, int* blocks, hipStream_t st, bool* lists) {
   if (p.aa_kind >= RT_AA_JITTERED) {
-    const size_t need = (size_t)blocks * 256 * 2 * (size_t)p.spp;
+    const size_t need = (size_t)*blocks * 256 * 2 * (size_t)p.spp;
     if (s->f64_tables.n < need) {
       HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffer
       int rc = s->f64_tables.alloc(need);
@@ -912,32 +924,51 @@ int launch_f64(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out
     }
     p.sample_scratch = s->f64_tables.p;
   }
-  // this call's pixel records (the float32 path's build, one launch set):
-  // a pixel whose camera rays provably miss the mesh skips their traversal,
-  // and its shadow rays to the lights its skip bits clear skip theirs —
-  // the same answers (the traversal would find no face), so frames and
-  // Stats stay bit-exact (tests/test_gpu_parity.py)
-  const bool binning = !(o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_COUNT_TRAVERSAL));
-  bool lists = false;
+  *lists = false;
   if (binning && sampler_in_pixel(o->aa_kind) && s->skippable) {
     FastParams pf;
     std::memset(&pf, 0, sizeof pf);
     bool zeroed = false;
-    if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
-    if (lists) p.pix_info = s->fr.info.p;
+    if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, lists, &zeroed)) return rc;
+    if (*lists) p.pix_info = s->fr.info.p;
   }
-  // one pixel per wave (k_render_px64): akGrid with >= 64 samples per
-  // pixel; the camera rays search this call's pixel lists, the shadow rays
-  // to distant lights the scene's light grids (rt_device.h mesh_lists)
-  const int px64 = o->aa_kind == RT_AA_GRID && p.spp >= 64 && !(o->flags & (RT_FLAG_F64_PER_LANE | RT_FLAG_COUNT_TRAVERSAL))
+  if (!px_wave) return RT_OK;
+  if (*lists) {
+    p.pix_slots = s->fr.slots.p;
+    p.slot_lg = s->fr.slot_lg;
+  }
+  p.tri_rec0 = (int32_t)s->num_nodes;
+  const long long nbatch = ((long long)mp.nrows * mp.ncols + batch - 1) / batch;
+  const long long resident = (long long)std::max(1, blocks_per_cu) * s->num_cus;
+  *blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
+  return RT_OK;
+}
+
+// One pixel per wave in float64 (k_render_px64, k_aov64_px): akGrid with >= 64
+// samples per pixel, unless the caller keeps one pixel per lane.
+bool f64_px_wave(const rt_options* o, int spp) {
+  return o->aa_kind == RT_AA_GRID && spp >= 64 && !(o->flags & RT_FLAG_F64_PER_LANE);
+}
+
+// The float64 render: prepare_f64, then k_render_px64 (whose shadow rays to
+// distant lights search the scene's light grids, rt_device.h mesh_lists) or
+// k_render. *launched: blocks of the render kernel.
+int launch_f64(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, int* launched) {
+  RenderParams<double> p;
+  int blocks = 1;
+  fill_params<double>(s, s->f64, o, mp, d_out, p, &blocks);
+  s->last_general = p.ngroups;
+  if (p.ngroups == 0) return RT_OK;
+  const bool binning = !(o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_COUNT_TRAVERSAL));
+  const int px64 = f64_px_wave(o, p.spp) && !(o->flags & RT_FLAG_COUNT_TRAVERSAL)
                        ? (s->any_reflective && o->max_ray_depth >= 1 ? 2 : 1)
                        : 0;
+  bool lists = false;
+  if (int rc = prepare_f64(s, o, mp, binning, px64 != 0, rtmi_px64_batch(), px64 ? rtmi_px64_blocks_per_cu(px64) : 0, p,
+                           &blocks, st, &lists))
+    return rc;
   if (px64) {
-    if (lists) {
-      p.pix_slots = s->fr.slots.p;
-      p.slot_lg = s->fr.slot_lg;
-      p.lean_plane = s->lean64_plane;
-    }
+    if (lists) p.lean_plane = s->lean64_plane;
     if (binning && s->has_grids) {
       p.grids = s->grids.p;
       p.grid_off = s->grid_off.p;
@@ -957,10 +988,6 @@ int launch_f64(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out
       }
       if (s->sh64_ready) p.sh64 = s->sh64.p;
     }
-    p.tri_rec0 = (int32_t)s->num_nodes;
-    const long long nbatch = ((long long)mp.nrows * mp.ncols + rtmi_px64_batch() - 1) / rtmi_px64_batch();
-    const long long resident = (long long)std::max(1, rtmi_px64_blocks_per_cu(px64)) * s->num_cus;
-    blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
   }
   if (o->flags & RT_FLAG_TIMING) HIP_TRY(hipEventRecord(s->tev[1], st));  // after the per-call build
   const int e = rtmi_launch_render_f64(&p, blocks, px64, st);
@@ -1095,17 +1122,10 @@ int launch_tail(hipStream_t st, int ngroups, rt_scene::Order* measuring, DevBuf<
   return RT_OK;
 }
 
-// zero / nzero: the queue heads and / or Stats words every call clears
-// before its render kernels (a float32 call that builds pixel lists clears
-// them in its first build launch: one launch fewer).
-int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, bool reduce,
-           unsigned int* zero, int nzero) {
-  auto clear = [&]() -> int {
-    if (nzero > 0) HIP_TRY(hipMemsetAsync(zero, 0, (size_t)nzero * sizeof(unsigned int), st));
-    return RT_OK;
-  };
-  // what rt_scene_last_split / _last_batch report describes THIS call, even
-  // when it returns early or runs the float64 kernel
+// What rt_scene_last_split / _last_batch and their kin report describes THIS
+// call, even when it returns early, runs the float64 kernel or
+// renders feature buffers: every render-class call starts from here.
+void reset_report(rt_scene* s) {
   s->fr.counted = false;
   s->fr.listed = false;
   s->fr.uniform = false;
@@ -1116,6 +1136,28 @@ int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hi
   s->last_lean_kind = 0;
   s->last_general = 0;
   s->last_batched = 0;
+}
+
+// A render-class call's completion on stream st. One event per call: the
+// buffer set's `used` is also the scene's `done`.
+int record_done(rt_scene* s, hipStream_t st) {
+  HIP_TRY(hipEventRecord(s->fr.used, st));
+  s->fr.used_rec = true;
+  s->done = s->fr.used;
+  s->done_stream = st;
+  return RT_OK;
+}
+
+// zero / nzero: the queue heads and / or Stats words every call clears
+// before its render kernels (a float32 call that builds pixel lists clears
+// them in its first build launch: one launch fewer).
+int launch(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_out, hipStream_t st, bool reduce,
+           unsigned int* zero, int nzero) {
+  auto clear = [&]() -> int {
+    if (nzero > 0) HIP_TRY(hipMemsetAsync(zero, 0, (size_t)nzero * sizeof(unsigned int), st));
+    return RT_OK;
+  };
+  reset_report(s);
   int launched = 0;  // blocks of the render kernels (0: nothing to render)
   if (o->precision == RT_FP64) {
     if (int rc = clear()) return rc;
@@ -1211,11 +1253,7 @@ int render_device(rt_scene* s, const rt_options* o, const Mapping& mp, float* d_
   if (rc) return rc;
   if ((out || need_stats || (o->flags & RT_FLAG_COUNT_TRAVERSAL)) && (rc = flush_reduce(s, st))) return rc;
   if (s->timed) HIP_TRY(hipEventRecord(s->tev[2], st));
-  // one event per call: the set's `used` is also the scene's `done`
-  HIP_TRY(hipEventRecord(s->fr.used, st));
-  s->fr.used_rec = true;
-  s->done = s->fr.used;
-  s->done_stream = st;
+  if (int rc = record_done(s, st)) return rc;
   if (out) return read_stats(s, st, out);
   return RT_OK;
 }
@@ -1305,34 +1343,32 @@ extern "C" int rt_render_bands_device(rt_scene* s, const rt_options* o, float* d
   return render_device(s, o, mp, d_bands, (hipStream_t)stream, out);
 }
 
-// ---- feature buffers (rt_render_aovs*, rt_fast_aov.h) ------------------------
+// ---- feature buffers (rt_render_aovs*, rt_fast_aov.h; rt_render_aovs_f64*, rt_kernels_aov64.hip) ----
 namespace {
 
-// The rows of a feature-buffer call in either precision: one image row per
-// mapping row. *empty: no rows, nothing to do; otherwise a channel must be
-// wanted (any).
-int aov_rows(const rt_options* oc, int32_t y0, int32_t y1, bool any, Mapping* mp, bool* empty) {
+// What all four entry points check before they take the scene's lock.
+// precision: the frame's whose features the call renders. oc: the options the
+// call goes by — bias, max_ray_depth and every flag outside `keep` are not the
+// caller's to matter. *empty: no rows, nothing to do; otherwise a channel must
+// be wanted (any).
+int aov_check(const rt_scene* s, const rt_options* o, int32_t precision, uint32_t keep, bool any, int32_t y0, int32_t y1,
+              rt_options* oc, Mapping* mp, bool* empty) {
+  if (precision == RT_FP64 && o->precision == RT_FP32)
+    return fail(RT_E_INVALID, "rt_render_aovs_f64 renders the feature buffers of an RT_FP64 frame: "
+                              "rt_render_aovs is the RT_FP32 call");
+  *oc = *o;
+  oc->bias = 0.0;
+  oc->max_ray_depth = 0;
+  oc->flags = o->flags & keep;
+  if (int rc = check_options(s, oc)) return rc;
+  if (precision == RT_FP32 && o->precision != RT_FP32)
+    return fail(RT_E_UNSUPPORTED, "rt_render_aovs renders the feature buffers of an RT_FP32 frame (precision %d)",
+                o->precision);
+  // one image row per mapping row
   if (int rc = lines_mapping(oc, y0, y1, 1, 1, mp)) return rc;
   *empty = mp->nrows == 0;
   if (!*empty && !any) return fail(RT_E_INVALID, "no feature buffer requested: every channel is null");
   return RT_OK;
-}
-
-// What both forms check before they take the scene's lock. oc: the options the
-// call goes by — bias, max_ray_depth and every flag but RT_FLAG_NO_BINNING are
-// not the caller's to matter. *empty: no rows, nothing to do.
-int aov_check(const rt_scene* s, const rt_options* o, const rt_aov_buffers* b, int32_t y0, int32_t y1, rt_options* oc,
-              Mapping* mp, bool* empty) {
-  if (!s || !o || !b) return fail(RT_E_INVALID, "null argument");
-  *oc = *o;
-  oc->bias = 0.0;
-  oc->max_ray_depth = 0;
-  oc->flags = o->flags & RT_FLAG_NO_BINNING;
-  if (int rc = check_options(s, oc)) return rc;
-  if (o->precision != RT_FP32)
-    return fail(RT_E_UNSUPPORTED, "rt_render_aovs renders the feature buffers of an RT_FP32 frame (precision %d)",
-                o->precision);
-  return aov_rows(oc, y0, y1, b->alpha || b->depth || b->object || b->face || b->normal || b->albedo, mp, empty);
 }
 
 // How a feature-buffer call of either precision enters the scene (its lock
@@ -1347,16 +1383,7 @@ int aov_begin(rt_scene* s, hipStream_t st) {
   // sequence of renders alternates as if this call were not there)
   s->timed = false;
   s->pipe = false;
-  s->fr.counted = false;
-  s->fr.listed = false;
-  s->fr.uniform = false;
-  s->fr.ground = false;
-  s->mesh1 = false;
-  s->pending_reduce = 0;
-  s->last_lean = 0;
-  s->last_lean_kind = 0;
-  s->last_general = 0;
-  s->last_batched = 0;
+  reset_report(s);
   return RT_OK;
 }
 
@@ -1365,10 +1392,7 @@ int aov_end(rt_scene* s, hipStream_t st, int blocks, rt_stats* out) {
   s->pending_reduce = blocks * 4;
   if (out)
     if (int rc = flush_reduce(s, st)) return rc;
-  HIP_TRY(hipEventRecord(s->fr.used, st));
-  s->fr.used_rec = true;
-  s->done = s->fr.used;
-  s->done_stream = st;
+  if (int rc = record_done(s, st)) return rc;
   if (out) return read_stats(s, st, out);
   return RT_OK;
 }
@@ -1404,12 +1428,7 @@ int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov
     bool lists = false, masks = false;
     const bool records = pl.L == 64;
     if (int rc = frame_build(s, o, mp, p, records, false, false, false, zero, nzero, st, &lists, &zeroed)) return rc;
-    if (lists) {
-      p.pix_slots = s->fr.slots.p;
-      p.pix_cnt = s->fr.info.p;
-      p.slot_lg = s->fr.slot_lg;
-      if (records) p.pix_info = s->fr.info.p;
-    }
+    if (lists) pixel_lists(s, records, p);
     if (s->objbins) {
       if (int rc = frame_obj_masks(s, o, mp, st, &masks)) return rc;
       if (masks) p.obj_pix = s->fr.omask.p;
@@ -1429,58 +1448,9 @@ int aov_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov
   return aov_end(s, st, pl.blocks, out);
 }
 
-// The scene's staging buffer sized for the wanted channels of a host form
-// (rt_aov_stage.h): off[c] from *base.
-int aov_stage(rt_scene* s, const void* const host[kAovChannels], const size_t px_bytes[kAovChannels],
-              const rt_options* o, size_t off[kAovChannels], unsigned char** base) {
-  const size_t total = aov_stage_offsets(host, px_bytes, (size_t)o->width * (size_t)o->height, off);
-  // (the staging buffer's last user was a host call, which waited for its copies)
-  if (s->aov_stage.n < total)
-    if (int rc = s->aov_stage.alloc(total)) return rc;
-  *base = s->aov_stage.p;
-  return RT_OK;
-}
-
-// Rows [y0, y1) of the staged channels back to the caller, then the call's
-// Stats (which waits for the stream: the copies have landed).
-int aov_unstage(rt_scene* s, void* const host[kAovChannels], const size_t px_bytes[kAovChannels], const rt_options* o,
-                const size_t off[kAovChannels], int32_t y0, int32_t y1, hipStream_t st, rt_stats* out) {
-  for (int c = 0; c < kAovChannels; ++c) {
-    if (!host[c]) continue;
-    size_t begin, count;
-    aov_stage_rows(px_bytes[c], o->width, y0, y1, &begin, &count);
-    HIP_TRY(hipMemcpyAsync((unsigned char*)host[c] + begin, s->aov_stage.p + off[c] + begin, count,
-                           hipMemcpyDeviceToHost, st));
-  }
-  rt_stats local{};
-  if (int rc = flush_reduce(s, st)) return rc;
-  if (int rc = read_stats(s, st, &local)) return rc;
-  if (out) *out = local;
-  return RT_OK;
-}
-
-// ---- float64 feature buffers (rt_render_aovs_f64*, rt_kernels_aov64.hip) ------
-
-// aov_check's float64 twin. oc: bias and max_ray_depth are not the caller's
-// to matter, of the flags RT_FLAG_NO_BINNING and RT_FLAG_F64_PER_LANE are.
-int aov64_check(const rt_scene* s, const rt_options* o, const rt_aov_buffers64* b, int32_t y0, int32_t y1,
-                rt_options* oc, Mapping* mp, bool* empty) {
-  if (!s || !o || !b) return fail(RT_E_INVALID, "null argument");
-  if (o->precision == RT_FP32)
-    return fail(RT_E_INVALID, "rt_render_aovs_f64 renders the feature buffers of an RT_FP64 frame: "
-                              "rt_render_aovs is the RT_FP32 call");
-  *oc = *o;
-  oc->bias = 0.0;
-  oc->max_ray_depth = 0;
-  oc->flags = o->flags & (RT_FLAG_NO_BINNING | RT_FLAG_F64_PER_LANE);
-  if (int rc = check_options(s, oc)) return rc;
-  return aov_rows(oc, y0, y1, b->alpha || b->depth || b->object || b->face || b->normal || b->albedo, mp, empty);
-}
-
-// The float64 device body: launch_f64's preparation for camera rays alone —
-// the parameters, the stochastic samplers' table scratch, this call's pixel
-// records and face lists under the render's conditions, the one-pixel-per-wave
-// grid — and no light-grid shadow records: no shadow ray is traced.
+// The float64 device body: the float64 render's preparation (prepare_f64) for
+// camera rays alone — this call's pixel records and face lists under the
+// render's conditions, and no light-grid shadow records: no shadow ray is traced.
 int aov64_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_aov_buffers64& b, hipStream_t st,
                  rt_stats* out) {
   if (int rc = aov_begin(s, st)) return rc;
@@ -1488,34 +1458,11 @@ int aov64_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_a
   int blocks = 1;
   fill_params<double>(s, s->f64, o, mp, nullptr, p, &blocks);
   s->last_general = p.ngroups;
-  if (p.aa_kind >= RT_AA_JITTERED) {
-    const size_t need = (size_t)blocks * 256 * 2 * (size_t)p.spp;
-    if (s->f64_tables.n < need) {
-      HIP_TRY(hipStreamSynchronize(st));  // an earlier launch may still use the old buffer
-      if (int rc = s->f64_tables.alloc(need)) return rc;
-    }
-    p.sample_scratch = s->f64_tables.p;
-  }
+  const int px = f64_px_wave(o, p.spp) ? 1 : 0;
   bool lists = false;
-  if (!(o->flags & RT_FLAG_NO_BINNING) && sampler_in_pixel(o->aa_kind) && s->skippable) {
-    FastParams pf;
-    std::memset(&pf, 0, sizeof pf);
-    bool zeroed = false;
-    if (int rc = frame_build(s, o, mp, pf, true, false, false, false, nullptr, 0, st, &lists, &zeroed)) return rc;
-    if (lists) p.pix_info = s->fr.info.p;
-  }
-  // launch_f64's condition for k_render_px64
-  const int px = o->aa_kind == RT_AA_GRID && p.spp >= 64 && !(o->flags & RT_FLAG_F64_PER_LANE) ? 1 : 0;
-  if (px) {
-    if (lists) {
-      p.pix_slots = s->fr.slots.p;
-      p.slot_lg = s->fr.slot_lg;
-    }
-    p.tri_rec0 = (int32_t)s->num_nodes;
-    const long long nbatch = ((long long)mp.nrows * mp.ncols + rtmi_aov64_batch() - 1) / rtmi_aov64_batch();
-    const long long resident = (long long)std::max(1, rtmi_aov64_blocks_per_cu()) * s->num_cus;
-    blocks = (int)std::max(1LL, std::min({(nbatch + 3) / 4, resident, (long long)s->max_waves / 4}));
-  }
+  if (int rc = prepare_f64(s, o, mp, !(o->flags & RT_FLAG_NO_BINNING), px != 0, rtmi_aov64_batch(),
+                           px ? rtmi_aov64_blocks_per_cu() : 0, p, &blocks, st, &lists))
+    return rc;
   // the Stats accumulator (behind the queue heads, which no float64 kernel reads)
   HIP_TRY(hipMemsetAsync(s->queue.p + rt_scene::kQueueWords, 0, 2 * (size_t)kStatSlots * sizeof(unsigned int), st));
   Aov64Params q;
@@ -1531,95 +1478,114 @@ int aov64_device(rt_scene* s, const rt_options* o, const Mapping& mp, const rt_a
   return aov_end(s, st, blocks, out);
 }
 
+// What the two precisions' entry points differ in: the buffer struct B, its
+// channels' scalar type and bytes per pixel, the device body, and what
+// aov_check wants and keeps.
+template <class B>
+struct Aov;
+template <>
+struct Aov<rt_aov_buffers> {
+  using Scalar = float;
+  static constexpr const size_t* px_bytes = kAovPxBytes32;
+  static constexpr auto device = &aov_device;
+  static constexpr int32_t precision = RT_FP32;
+  static constexpr uint32_t keep = RT_FLAG_NO_BINNING;
+};
+template <>
+struct Aov<rt_aov_buffers64> {
+  using Scalar = double;
+  static constexpr const size_t* px_bytes = kAovPxBytes64;
+  static constexpr auto device = &aov64_device;
+  static constexpr int32_t precision = RT_FP64;
+  static constexpr uint32_t keep = RT_FLAG_NO_BINNING | RT_FLAG_F64_PER_LANE;
+};
+
+// The frame of both forms: the checks; no rows: zero Stats; else body(oc, mp)
+// with the scene's lock held and its device current.
+template <class B, class Body>
+int aov_call(rt_scene* s, const rt_options* o, const B* b, int32_t y0, int32_t y1, rt_stats* out, Body body) {
+  if (!s || !o || !b) return fail(RT_E_INVALID, "null argument");
+  rt_options oc;
+  Mapping mp;
+  bool empty = false;
+  const bool any = b->alpha || b->depth || b->object || b->face || b->normal || b->albedo;
+  if (int rc = aov_check(s, o, Aov<B>::precision, Aov<B>::keep, any, y0, y1, &oc, &mp, &empty)) return rc;
+  if (empty) {
+    if (out) *out = rt_stats{};
+    return RT_OK;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard g(s->device);
+  return body(oc, mp);
+}
+
+// Device form: d_out's pointers are device memory.
+template <class B>
+int aov_device_form(rt_scene* s, const rt_options* o, const B* d_out, int32_t y0, int32_t y1, void* stream,
+                    rt_stats* out) {
+  return aov_call(s, o, d_out, y0, y1, out, [&](const rt_options& oc, const Mapping& mp) {
+    return Aov<B>::device(s, &oc, mp, *d_out, (hipStream_t)stream, out);
+  });
+}
+
+// Host form: the wanted channels' device copies in the scene's staging buffer
+// (rt_stage.h), rendered on the scene's own stream; rows [y0, y1) come back,
+// then the call's Stats (which waits for the stream: the copies have landed).
+template <class B>
+int aov_host_form(rt_scene* s, const rt_options* o, const B* out_bufs, int32_t y0, int32_t y1, rt_stats* out) {
+  using S = typename Aov<B>::Scalar;
+  return aov_call(s, o, out_bufs, y0, y1, out, [&](const rt_options& oc, const Mapping& mp) -> int {
+    void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
+                                      out_bufs->face,  out_bufs->normal, out_bufs->albedo};
+    const StageLayout l = aov_stage_layout(host, Aov<B>::px_bytes, (size_t)o->width * (size_t)o->height);
+    // (the staging buffer's last user was a host call, which waited for its copies)
+    if (s->aov_stage.n < l.total)
+      if (int rc = s->aov_stage.alloc(l.total)) return rc;
+    unsigned char* const base = s->aov_stage.p;
+    B d{};
+    d.alpha = host[0] ? (S*)(base + l.off[0]) : nullptr;
+    d.depth = host[1] ? (S*)(base + l.off[1]) : nullptr;
+    d.object = host[2] ? (int32_t*)(base + l.off[2]) : nullptr;
+    d.face = host[3] ? (int32_t*)(base + l.off[3]) : nullptr;
+    d.normal = host[4] ? (S*)(base + l.off[4]) : nullptr;
+    d.albedo = host[5] ? (S*)(base + l.off[5]) : nullptr;
+    hipStream_t st = s->stream;
+    if (int rc = Aov<B>::device(s, &oc, mp, d, st, nullptr)) return rc;
+    for (int c = 0; c < kAovChannels; ++c) {
+      if (!host[c]) continue;
+      size_t begin, count;
+      aov_stage_rows(Aov<B>::px_bytes[c], o->width, y0, y1, &begin, &count);
+      HIP_TRY(hipMemcpyAsync((unsigned char*)host[c] + begin, base + l.off[c] + begin, count, hipMemcpyDeviceToHost,
+                             st));
+    }
+    rt_stats local{};
+    if (int rc = flush_reduce(s, st)) return rc;
+    if (int rc = read_stats(s, st, &local)) return rc;
+    if (out) *out = local;
+    return RT_OK;
+  });
+}
+
 }  // namespace
-
-extern "C" int rt_render_aovs_f64_device(rt_scene* s, const rt_options* o, const rt_aov_buffers64* d_out, int32_t y0,
-                                         int32_t y1, void* stream, rt_stats* out) {
-  rt_options oc;
-  Mapping mp;
-  bool empty = false;
-  if (int rc = aov64_check(s, o, d_out, y0, y1, &oc, &mp, &empty)) return rc;
-  if (empty) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  return aov64_device(s, &oc, mp, *d_out, (hipStream_t)stream, out);
-}
-
-extern "C" int rt_render_aovs_f64(rt_scene* s, const rt_options* o, const rt_aov_buffers64* out_bufs, int32_t y0,
-                                  int32_t y1, rt_stats* out) {
-  rt_options oc;
-  Mapping mp;
-  bool empty = false;
-  if (int rc = aov64_check(s, o, out_bufs, y0, y1, &oc, &mp, &empty)) return rc;
-  if (empty) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
-                                    out_bufs->face,  out_bufs->normal, out_bufs->albedo};
-  size_t off[kAovChannels];
-  unsigned char* base = nullptr;
-  if (int rc = aov_stage(s, host, kAovPxBytes64, o, off, &base)) return rc;
-  rt_aov_buffers64 d{};
-  d.alpha = host[0] ? (double*)(base + off[0]) : nullptr;
-  d.depth = host[1] ? (double*)(base + off[1]) : nullptr;
-  d.object = host[2] ? (int32_t*)(base + off[2]) : nullptr;
-  d.face = host[3] ? (int32_t*)(base + off[3]) : nullptr;
-  d.normal = host[4] ? (double*)(base + off[4]) : nullptr;
-  d.albedo = host[5] ? (double*)(base + off[5]) : nullptr;
-  hipStream_t st = s->stream;
-  if (int rc = aov64_device(s, &oc, mp, d, st, nullptr)) return rc;
-  return aov_unstage(s, host, kAovPxBytes64, o, off, y0, y1, st, out);
-}
 
 extern "C" int rt_render_aovs_device(rt_scene* s, const rt_options* o, const rt_aov_buffers* d_out, int32_t y0,
                                      int32_t y1, void* stream, rt_stats* out) {
-  rt_options oc;
-  Mapping mp;
-  bool empty = false;
-  if (int rc = aov_check(s, o, d_out, y0, y1, &oc, &mp, &empty)) return rc;
-  if (empty) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  return aov_device(s, &oc, mp, *d_out, (hipStream_t)stream, out);
+  return aov_device_form(s, o, d_out, y0, y1, stream, out);
 }
 
 extern "C" int rt_render_aovs(rt_scene* s, const rt_options* o, const rt_aov_buffers* out_bufs, int32_t y0, int32_t y1,
                               rt_stats* out) {
-  rt_options oc;
-  Mapping mp;
-  bool empty = false;
-  if (int rc = aov_check(s, o, out_bufs, y0, y1, &oc, &mp, &empty)) return rc;
-  if (empty) {
-    if (out) *out = rt_stats{};
-    return RT_OK;
-  }
-  std::lock_guard<std::mutex> lk(s->mu);
-  DeviceGuard g(s->device);
-  // the wanted channels' device copies (rt_aov_stage.h); only rows [y0, y1) come back
-  void* const host[kAovChannels] = {out_bufs->alpha, out_bufs->depth,  out_bufs->object,
-                                    out_bufs->face,  out_bufs->normal, out_bufs->albedo};
-  size_t off[kAovChannels];
-  unsigned char* base = nullptr;
-  if (int rc = aov_stage(s, host, kAovPxBytes32, o, off, &base)) return rc;
-  rt_aov_buffers d{};
-  d.alpha = host[0] ? (float*)(base + off[0]) : nullptr;
-  d.depth = host[1] ? (float*)(base + off[1]) : nullptr;
-  d.object = host[2] ? (int32_t*)(base + off[2]) : nullptr;
-  d.face = host[3] ? (int32_t*)(base + off[3]) : nullptr;
-  d.normal = host[4] ? (float*)(base + off[4]) : nullptr;
-  d.albedo = host[5] ? (float*)(base + off[5]) : nullptr;
-  hipStream_t st = s->stream;
-  if (int rc = aov_device(s, &oc, mp, d, st, nullptr)) return rc;
-  return aov_unstage(s, host, kAovPxBytes32, o, off, y0, y1, st, out);
+  return aov_host_form(s, o, out_bufs, y0, y1, out);
+}
+
+extern "C" int rt_render_aovs_f64_device(rt_scene* s, const rt_options* o, const rt_aov_buffers64* d_out, int32_t y0,
+                                         int32_t y1, void* stream, rt_stats* out) {
+  return aov_device_form(s, o, d_out, y0, y1, stream, out);
+}
+
+extern "C" int rt_render_aovs_f64(rt_scene* s, const rt_options* o, const rt_aov_buffers64* out_bufs, int32_t y0,
+                                  int32_t y1, rt_stats* out) {
+  return aov_host_form(s, o, out_bufs, y0, y1, out);
 }
 
 extern "C" int rt_scene_last_stats(rt_scene* s, rt_stats* out) {

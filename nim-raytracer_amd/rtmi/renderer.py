@@ -12,6 +12,7 @@ uploaded once (BVH built) — the Nim shim in INTEGRATION.md does the same.
 import contextlib
 import ctypes as C
 import threading
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -184,13 +185,13 @@ class DeviceScene:
             if d.shape[0] != n:
                 raise ValueError("orig and dir must hold the same number of rays")
             tn = None if t_near is None else _host_f64(t_near, (n,))
-            return self._query_host(n, flags, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays(
+            return self._query_host(_HITS64, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays(
                 self.h, n, _dptr(o), _dptr(d), _dptr(tn), flags, hits, nrm, st))
         n = _dev_f64(orig, None, 3)
         _dev_f64(dir, n, 3)
         if t_near is not None:
             _dev_f64(t_near, n, 1)
-        return self._query_device(orig, n, flags, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_device(
+        return self._query_device(_HITS64, orig, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_device(
             self.h, n, C.c_void_p(orig.data_ptr()), C.c_void_p(dir.data_ptr()),
             C.c_void_p(t_near.data_ptr()) if t_near is not None else None, flags, hits, nrm, _stream(stream), st))
 
@@ -207,10 +208,10 @@ class DeviceScene:
         if _is_host(xy):
             p = _host_f64(xy, (-1, 2))
             n = p.shape[0]
-            return self._query_host(n, flags, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels(
+            return self._query_host(_HITS64, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels(
                 self.h, C.byref(o), n, _dptr(p), flags, hits, nrm, st))
         n = _dev_f64(xy, None, 2)
-        return self._query_device(xy, n, flags, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_device(
+        return self._query_device(_HITS64, xy, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_device(
             self.h, C.byref(o), n, C.c_void_p(xy.data_ptr()), flags, hits, nrm, _stream(stream), st))
 
     # -- radiance queries (rt_shade_rays*) -----------------------------------
@@ -331,13 +332,13 @@ class DeviceScene:
             tn = None if t_near is None else _host_f32n(t_near, 1)
             if tn is not None and tn.shape[0] != n:
                 raise ValueError("t_near must hold one value per ray")
-            return self._query32_host(n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32(
+            return self._query_host(_HITS32, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32(
                 self.h, n, _fptr(o), _fptr(d), _fptr(tn), flags, hits, nrm, st))
         n = _dev_f32(orig, None)
         _dev_f32(dir, n)
         if t_near is not None:
             _dev_f32n(t_near, n, 1)
-        return self._query32_device(orig, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32_device(
+        return self._query_device(_HITS32, orig, n, normals, stats, lambda hits, nrm, st: lib().rt_trace_rays_f32_device(
             self.h, n, C.c_void_p(orig.data_ptr()), C.c_void_p(dir.data_ptr()),
             C.c_void_p(t_near.data_ptr()) if t_near is not None else None, flags, hits, nrm, _stream(stream), st))
 
@@ -354,10 +355,10 @@ class DeviceScene:
         if _is_host(xy):
             p = _host_f32n(xy, 2)
             n = p.shape[0]
-            return self._query32_host(n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32(
+            return self._query_host(_HITS32, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32(
                 self.h, C.byref(o), n, _fptr(p), flags, hits, nrm, st))
         n = _dev_f32n(xy, None, 2)
-        return self._query32_device(xy, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32_device(
+        return self._query_device(_HITS32, xy, n, normals, stats, lambda hits, nrm, st: lib().rt_pick_pixels_f32_device(
             self.h, C.byref(o), n, C.c_void_p(xy.data_ptr()), flags, hits, nrm, _stream(stream), st))
 
     def trace32_subset(self):
@@ -448,42 +449,26 @@ class DeviceScene:
             check(call(self.h, C.byref(o), C.byref(bufs), int(y0), y1, _stream(stream), pst))
         return (res, Stats.from_c(st)) if stats else res
 
-    def _query32_host(self, n, normals, stats, call):
-        hits = np.zeros(n, dtype=_HIT32_DTYPE)
-        nrm = np.zeros((n, 3), dtype=np.float32) if normals else None
+    def _query_host(self, k, n, normals, stats, call):
+        """The host form of a hit query in precision k (_HITS): the hits and normals made here."""
+        hits = np.zeros(n, dtype=k.rec)
+        nrm = np.zeros((n, 3), dtype=k.scalar) if normals else None
         st = abi.rt_stats()
-        check(call(hits.ctypes.data_as(C.POINTER(abi.rt_hit32)), _fptr(nrm), C.byref(st) if stats else None))
+        check(call(hits.ctypes.data_as(C.POINTER(k.hit)), k.ptr(nrm), C.byref(st) if stats else None))
         out = (hits["t"].copy(), hits["obj"].copy(), hits["face"].copy())
         return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
 
-    def _query32_device(self, like, n, normals, stats, call):
+    def _query_device(self, k, like, n, normals, stats, call):
+        """The device form: t / obj / face are views of one (n, k.width) hit tensor."""
         import torch
-        hits = torch.empty((n, 4), dtype=torch.float32, device=like.device)
-        nrm = torch.empty((n, 3), dtype=torch.float32, device=like.device) if normals else None
+        dt = getattr(torch, np.dtype(k.scalar).name)
+        hits = torch.empty((n, k.width), dtype=dt, device=like.device)
+        nrm = torch.empty((n, 3), dtype=dt, device=like.device) if normals else None
         st = abi.rt_stats()
         check(call(C.c_void_p(hits.data_ptr()), C.c_void_p(nrm.data_ptr()) if normals else None,
                    C.byref(st) if stats else None))
         words = hits.view(torch.int32)
-        out = (hits[:, 0], words[:, 1], words[:, 2])
-        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
-
-    def _query_host(self, n, flags, normals, stats, call):
-        hits = np.zeros(n, dtype=_HIT_DTYPE)
-        nrm = np.zeros((n, 3), dtype=np.float64) if normals else None
-        st = abi.rt_stats()
-        check(call(hits.ctypes.data_as(C.POINTER(abi.rt_hit)), _dptr(nrm), C.byref(st) if stats else None))
-        out = (hits["t"].copy(), hits["obj"].copy(), hits["face"].copy())
-        return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
-
-    def _query_device(self, like, n, flags, normals, stats, call):
-        import torch
-        hits = torch.empty((n, 2), dtype=torch.float64, device=like.device)
-        nrm = torch.empty((n, 3), dtype=torch.float64, device=like.device) if normals else None
-        st = abi.rt_stats()
-        check(call(C.c_void_p(hits.data_ptr()), C.c_void_p(nrm.data_ptr()) if normals else None,
-                   C.byref(st) if stats else None))
-        words = hits.view(torch.int32)
-        out = (hits[:, 0], words[:, 2], words[:, 3])
+        out = (hits[:, 0], words[:, k.obj], words[:, k.face])
         return out + ((nrm,) if normals else ()) + ((Stats.from_c(st),) if stats else ())
 
     def last_pipelined(self):
@@ -1135,6 +1120,14 @@ def _fptr(a):
 
 def _dptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# A hit query's arrays in each precision: the numpy record and the ABI struct
+# of a hit, the scalar type of t and the normals with its pointer maker, and
+# the device form's hit tensor: its width in scalars and the 32-bit word
+# columns of obj / face.
+_HITS64 = SimpleNamespace(rec=_HIT_DTYPE, hit=abi.rt_hit, scalar=np.float64, ptr=_dptr, width=2, obj=2, face=3)
+_HITS32 = SimpleNamespace(rec=_HIT32_DTYPE, hit=abi.rt_hit32, scalar=np.float32, ptr=_fptr, width=4, obj=1, face=2)
 
 
 def _dev_f64(t, n, width):
